@@ -27,6 +27,14 @@ Multi-GPU: one process per GPU (torchrun), each rank runs its own images
 gradient all-reduce per step), barrier +
 synchronize around the timed region, time = max over ranks, value = all
 images / that time (weak scaling).
+
+A plain run sets up, warms up, times --steps steps and prints the result line
+(value, ms_per_step, the live per-kernel figures of the one event-timed step).
+--full adds what takes runs of its own: the box calibration (vendor GEMM +
+p2 conv) and the clock / power sampler, the fixed-rows training region, and
+the CPU baseline.  --dump-outputs DIR writes what the last timed step
+returned (training: its loss terms; inference: the instances) as
+DIR/<name>.npy.
 """
 import argparse
 import json
@@ -79,6 +87,15 @@ def parse():
     p.add_argument("--model", default="mask_rcnn_R_50_FPN", choices=sorted(CONFIGS))
     p.add_argument("--height", type=int, default=800)
     p.add_argument("--width", type=int, default=1333)
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the box calibration "
+                        "and clock / power sampler, the fixed-rows region (--fixed-rows-steps) "
+                        "and the CPU baseline (--cpu-baseline, --cpu-one-core); without it "
+                        "those options have no effect")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned as "
+                        "DIR/<name>.npy (float32 / float64; at most 64 MB in all, larger "
+                        "arrays as a fixed seeded sample of their elements)")
     p.add_argument("--cpu-baseline", type=int, default=1, help="time the CPU oracle (rank 0, N=1)")
     p.add_argument("--cpu-images", type=int, default=2, help="images per CPU iteration (<= batch)")
     p.add_argument("--cpu-iters", type=int, default=5,
@@ -648,6 +665,52 @@ def fixed_rows_region(args, trainer, batch, rh, world, device):
                     "on every sampled foreground slot (roi_heads.mask_compact_rows = False)"}
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6   # of array data: under 64 MB with the .npy headers
+
+
+def _named_tensors(out, prefix=""):
+    """(name, tensor) for every tensor / number in a step's nested output."""
+    if isinstance(out, dict):
+        for k in sorted(out):
+            yield from _named_tensors(out[k], f"{prefix}.{k}" if prefix else str(k))
+    elif isinstance(out, (list, tuple)):
+        for i, v in enumerate(out):
+            yield from _named_tensors(v, f"{prefix}.{i}" if prefix else str(i))
+    elif isinstance(out, (torch.Tensor, int, float, bool)):
+        yield prefix or "out", torch.as_tensor(out)
+    elif out is not None:
+        raise TypeError(f"--dump-outputs: {prefix or 'out'} is a {type(out).__name__}, not an array")
+
+
+def dump_outputs(out, directory, limit=DUMP_LIMIT_BYTES):
+    """Write what a caller of the timed step received (``out`` of the last
+    timed step) as ``directory``/<name>.npy: float64 for 64-bit values, else
+    float32.  At most ``limit`` bytes in all: every array gets an equal share,
+    and a larger one is stored as the elements at fixed seeded flat positions
+    (sorted; the same positions for the same shape from run to run).  Returns
+    {name: {"shape", "stored"}} for the result line."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    items = [(n.replace(os.sep, "_"), t.detach()) for n, t in _named_tensors(out)]
+    share = limit // max(1, len(items))
+    info = {}
+    for name, t in items:
+        wide = t.element_size() == 8
+        keep = share // (8 if wide else 4)
+        flat = t.reshape(-1)
+        if flat.numel() > keep:
+            g = torch.Generator(device="cpu").manual_seed(0)
+            idx = torch.randint(flat.numel(), (keep,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+            shape = (keep,)
+        else:
+            shape = tuple(t.shape)
+        arr = flat.to(torch.float64 if wide else torch.float32).cpu().numpy().reshape(shape)
+        np.save(os.path.join(directory, name + ".npy"), arr)
+        info[name] = {"shape": list(t.shape), "stored": int(arr.size)}
+    return info
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -703,10 +766,10 @@ def main():
         for _ in range(args.warmup):
             out = step()
         torch.cuda.synchronize()
-        # box calibration (fixed vendor GEMM + this repo's p2 conv) and the
-        # clock / power sampler: outside the timed region
-        calib = box_calibration(device) if not args.no_calibration else {}
-        sampler = GpuSampler(device)
+        # --full: box calibration (fixed vendor GEMM + this repo's p2 conv) and
+        # the clock / power sampler: outside the timed region
+        calib = box_calibration(device) if args.full and not args.no_calibration else {}
+        sampler = GpuSampler(device) if args.full else None
         torch.cuda.synchronize()
         if world > 1:
             torch.distributed.barrier()
@@ -718,7 +781,8 @@ def main():
         sample = args.steps - 1 if args.timed_step_sample < 0 else min(args.timed_step_sample,
                                                                         args.steps - 1)
         torch.cuda.nvtx.range_push("timed_region")  # roctx: tools/prof_window.py
-        sampler.start()
+        if sampler is not None:
+            sampler.start()
         t0 = time.perf_counter()
         reducer = trainer.reducer if args.mode == "train" else None
         for i in range(args.steps):
@@ -731,7 +795,8 @@ def main():
         if world > 1:
             torch.distributed.barrier()
         elapsed = time.perf_counter() - t0
-        sampler.stop()
+        if sampler is not None:
+            sampler.stop()
         torch.cuda.nvtx.range_pop()
         KernelTimer.enabled = False
     summary = KernelTimer.summary()
@@ -740,11 +805,14 @@ def main():
         t = torch.tensor([elapsed], device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(out, args.dump_outputs)
     fixed_rows = None
     rh = getattr(model, "roi_heads", None)
     main_rows = getattr(rh, "last_mask_rows", None)
-    if (args.mode == "train" and args.fixed_rows_steps > 0 and not args.mask_fixed_rows
-            and getattr(rh, "mask_on", False)):
+    if (args.full and args.mode == "train" and args.fixed_rows_steps > 0
+            and not args.mask_fixed_rows and getattr(rh, "mask_on", False)):
         fixed_rows = fixed_rows_region(args, trainer, batch, rh, world, device)
     _C.raise_on_errors(device)
     in_sync = None
@@ -812,12 +880,14 @@ def main():
             "roofline": kernels.get("conv2d_split", kernels.get("conv2d_mfma")),
             **({"replicas_in_sync": in_sync} if in_sync is not None else {}),
             "kernels": kernels,
+            **({"dumped_outputs": dumped} if dumped is not None else {}),
+        }
+        if args.full:
             # this box: a fixed vendor GEMM + this repo's p2 conv timed in the
             # same process before the timed region, and the clocks / power
             # sampled during it (a slow box vs a code regression)
-            "box": dict(calib, gpu_during_timed_region=sampler.summary()),
-        }
-        if args.cpu_baseline and world == 1:
+            result["box"] = dict(calib, gpu_during_timed_region=sampler.summary())
+        if args.full and args.cpu_baseline and world == 1:
             result["cpu_baseline"] = cpu_baseline(args, model, batch, cfg)
         print(json.dumps(result), flush=True)
     if world > 1:

@@ -22,3 +22,45 @@ def test_kernel_report_fractions_and_roi_backward_accounting():
         want = roi["traffic"] / 0.255e-3 / 1e9
         assert abs(roi["achieved_counter"] - want) < 0.2
         assert roi["frac_counter"] < 1
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """--dump-outputs: every tensor of a step's nested output becomes
+    <name>.npy in float32 (float64 for 64-bit values); an array over its share
+    of the byte limit is stored as the same seeded sample on every call."""
+    import numpy as np
+    import torch
+    import bench
+    masks = (torch.arange(2 * 3 * 40 * 50) % 251).to(torch.uint8).reshape(2, 3, 40, 50)
+    out = {"instances": {"masks": masks, "boxes": torch.rand(2, 3, 4),
+                         "classes": torch.arange(6).reshape(2, 3)},
+           "total_loss": torch.tensor(1.25, dtype=torch.float64)}
+    limit = 4096
+    a, b = tmp_path / "a", tmp_path / "b"
+    info = bench.dump_outputs(out, str(a), limit=limit)
+    bench.dump_outputs(out, str(b), limit=limit)
+    names = sorted(p.name for p in a.iterdir())
+    assert names == ["instances.boxes.npy", "instances.classes.npy", "instances.masks.npy",
+                     "total_loss.npy"]
+    got = {n: np.load(a / n) for n in names}
+    assert sum(v.nbytes for v in got.values()) <= limit
+    assert got["instances.boxes.npy"].dtype == np.float32
+    assert np.array_equal(got["instances.boxes.npy"], out["instances"]["boxes"].numpy())
+    assert got["instances.classes.npy"].dtype == np.float64
+    assert got["total_loss.npy"].dtype == np.float64 and got["total_loss.npy"] == 1.25
+    m = got["instances.masks.npy"]
+    assert m.dtype == np.float32 and m.shape == (limit // 4 // 4,)
+    assert info["instances.masks"] == {"shape": [2, 3, 40, 50], "stored": m.size}
+    assert set(m.tolist()) <= set(range(251)) and len(set(m.tolist())) > 1
+    for n in names:
+        assert np.array_equal(got[n], np.load(b / n))
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    import bench
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert (args.full, args.dump_outputs, args.steps, args.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full and args.dump_outputs == "d"

@@ -8,7 +8,7 @@ reps=$1; tag=$2; shift 2
 for rep in $(seq 1 $reps); do
   for tree in "$@"; do
     echo "== rep $rep tree $tree" >&2
-    (cd $tree && timeout -k 10 300 python bench.py --steps 20 --warmup 5 --cpu-baseline 0) \
+    (cd $tree && timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full --cpu-baseline 0) \
       > gpurun_out/${tag}_last.out 2> gpurun_out/${tag}_last.err || { cat gpurun_out/${tag}_last.err >&2; exit 1; }
     tail -1 gpurun_out/${tag}_last.out | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); d['tree']='$tree'; d['rep']=$rep
