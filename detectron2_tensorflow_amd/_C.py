@@ -163,6 +163,9 @@ _SIGS = {
     "d2mi_fold_many_sizes": (c_int, [P, P]),
     "d2mi_fold_frozen_bn_many": (c_int, [P, c_int, c_int, P]),
     "d2mi_fold_frozen_bn_bwd_many": (c_int, [P, c_int, c_int, c_int, P, P]),
+    "d2mi_deform_sample_fwd": (c_int, [P, P] + [c_int] * 11 + [P, P]),
+    "d2mi_deform_sample_bwd_workspace_size": (c_size_t, [c_int] * 10),
+    "d2mi_deform_sample_bwd": (c_int, [P, P, P] + [c_int] * 12 + [P, P, P, c_size_t, P]),
 }
 
 EXPORTED = tuple(_SIGS)

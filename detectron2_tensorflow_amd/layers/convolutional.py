@@ -729,6 +729,144 @@ class Conv2D(Layer):
 
 
 @add_arg_scope
+class DeformConv2D(Conv2D):
+    """Deformable conv v1 (convolutional.py:267-503), GPU only.
+
+    call = offset conv (``offset_weights`` / ``offset_bias``, zero-initialised,
+    over the SAME-padded input, VALID) -> ops.deform_sample (the bilinear
+    gather, d2mi_deform_sample_fwd) -> the main product as a 1x1 MFMA conv of
+    the column matrix [N,OH,OW,k*k*C] with ``weights.reshape(1,1,k*k*C,Cout)``,
+    whose epilogue, dgrad and wgrad are Conv2D's (_ConvMFMAFn): the FrozenBN
+    fold, the fused ReLU with its ``_d2mi_relu_info`` tag, ``residual`` and
+    ``final_relu`` work as there.
+
+    The offset conv runs on the MFMA conv too (rate 1): its 2*G*k*k = 18
+    output channels are padded to a multiple of 4 by concatenating constant
+    zero columns to the weight and bias views (the parameters keep the
+    reference shapes); the sampler reads the padded rows through its row
+    stride and gives the pad channels a zero gradient.  A dilated offset conv
+    (rate > 1) runs on the library conv, as a dilated Conv2D does.
+
+    The folded weights are packed in the 1x1 layout [1,1,Cout,k*k*C] here
+    (wants_packed is False: FoldGroup must not emit the 3x3 [k,k,Cout,C]
+    packing for this layer)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding="SAME", rate=1,
+                 num_groups=1, deform_num_groups=1, use_bias=True, activation=None,
+                 normalizer=None, normalizer_params=None, weights_initializer=None,
+                 weights_regularizer=None, bias_initializer=None, bias_regularizer=None,
+                 variables_collections=None, trainable=True, outputs_collections=None, **kwargs):
+        if in_channels % deform_num_groups != 0:
+            raise ValueError(f'"in_channels" {in_channels} is not divisible by '
+                             f'"deform_num_groups" {deform_num_groups}.')
+        if num_groups != 1:
+            raise NotImplementedError(
+                "grouped deformable convs (num_groups > 1) are not implemented: no shipped "
+                "config uses them")
+        if kernel_size not in (1, 3):
+            raise NotImplementedError("DeformConv2D: kernel_size 1 and 3 are implemented")
+        kwargs.pop("impl", None)  # (an arg-scope default for Conv2D: always the HIP path here)
+        Conv2D.__init__(self, in_channels, out_channels, kernel_size, stride=stride,
+                        padding=padding, rate=rate, num_groups=1, use_bias=use_bias,
+                        activation=activation, normalizer=normalizer,
+                        normalizer_params=normalizer_params,
+                        weights_initializer=weights_initializer,
+                        weights_regularizer=weights_regularizer,
+                        bias_initializer=None,  # the reference forces zeros (:311)
+                        bias_regularizer=bias_regularizer, trainable=trainable, impl="mfma",
+                        deform_num_groups=deform_num_groups, **kwargs)
+
+    def build(self):
+        super().build()
+        k = self.kernel_size
+        oc = self.offset_channels = 2 * self.deform_num_groups * k * k
+        self.offset_weights = torch.nn.Parameter(torch.zeros(k, k, self.in_channels, oc),
+                                                 requires_grad=self.trainable)
+        self.offset_bias = torch.nn.Parameter(torch.zeros(oc), requires_grad=self.trainable)
+        padc = (-oc) % 4
+        # constant zero columns for the MFMA offset conv (not variables)
+        self.register_buffer("_offset_pad_w", torch.zeros(k, k, self.in_channels, padc),
+                             persistent=False)
+        self.register_buffer("_offset_pad_b", torch.zeros(padc), persistent=False)
+        self._offset_packed = None
+        self._offset_packed_key = None
+        self._cols_packed = None
+        self._cols_packed_key = None
+
+    def wants_packed(self):
+        return False
+
+    def _offsets(self, x, pads):
+        """[N,OH,OW,>= offset_channels]: the offset conv (:380-406)."""
+        if self.rate != 1 or self.in_channels % 4 != 0:
+            xp = F.pad(x, (0, 0, pads[0], pads[1], pads[0], pads[1])) if any(pads) else x
+            y = F.conv2d(xp.permute(0, 3, 1, 2), self.offset_weights.permute(3, 2, 0, 1),
+                         self.offset_bias, stride=self.stride, dilation=self.rate)
+            return y.permute(0, 2, 3, 1).contiguous()
+        w, b = self.offset_weights, self.offset_bias
+        if self._offset_pad_b.numel():
+            w = torch.cat([w, self._offset_pad_w], 3)
+            b = torch.cat([b, self._offset_pad_b])
+        ow = self.offset_weights
+        key = (ow.data_ptr(), ow._version)
+        if self._offset_packed is None or self._offset_packed_key != key:
+            self._offset_packed = ops.pack_conv_weights(w.detach())
+            self._offset_packed_key = key
+        return _ConvMFMAFn.apply(x, w, b, self._offset_packed, self.stride, pads, False, None)
+
+    def call(self, inputs, residual=None, final_relu=False, res_grad_to=None, raw=False):
+        """residual / final_relu / res_grad_to / raw: as Conv2D.call.  The input
+        has two readers here (the offset conv and the sampler), so there is no
+        relu_input_sole_consumer: the producer keeps its own ReLU backward."""
+        if not inputs.is_cuda:
+            raise ValueError(f"{self.scope}: DeformConv2D runs on the GPU (HIP) only, got a "
+                             f"tensor on {inputs.device}")
+        if final_relu and self.act_fn is not None:
+            raise ValueError("final_relu is for layers without an activation")
+        k = self.kernel_size
+        w, b, norm, _ = self.effective_params()
+        pads = same_pads(k, self.rate) if (self.padding == "SAME" and k != 1) else (0, 0)
+        offsets = self._offsets(inputs, pads)
+        cols = ops.deform_sample(inputs, offsets, k, self.stride, self.rate, pads,
+                                 self.deform_num_groups)
+        w1 = w.reshape(1, 1, k * k * self.in_channels, self.out_channels)
+        key = self._param_key()
+        if torch.is_grad_enabled() and self.fold_trainable():
+            packed = ops.pack_conv_weights(w1.detach())
+        else:  # constant weights: packed once per parameter version
+            if self._cols_packed is None or self._cols_packed_key != key:
+                self._cols_packed = ops.pack_conv_weights(w1.detach())
+                self._cols_packed_key = key
+            packed = self._cols_packed
+        fuse_relu = norm is None and (is_relu(self.act_fn) or final_relu)
+        ret = _ConvMFMAFn.apply(cols, w1, b, packed, 1, (0, 0), fuse_relu, None, residual,
+                                bool(final_relu), False, res_grad_to)
+        if raw:
+            return ret
+        if norm is not None:
+            ret = norm(ret)
+        if self.act_fn is not None and not fuse_relu:
+            ret = self.act_fn(ret)
+        if final_relu and not fuse_relu:
+            ret = torch.relu(ret)
+        return ret
+
+
+@add_arg_scope
+class ModulatedDeformConv2D(Layer):
+    """The reference's ModulatedDeformConv2D (convolutional.py:506-745) can be
+    neither constructed nor called, so there is no behaviour to match."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError(
+            "ModulatedDeformConv2D: the reference class cannot be constructed or called, so "
+            "there is no behaviour to match -- convolutional.py:536 calls "
+            "super(DeformConv2D, self).__init__ (a TypeError), :653-659 reshape 3*G*k*k offset "
+            "channels to [..., 2] and then read offset[..., 2], :677 uses an undefined `batch`, "
+            "and :727 calls a missing self.group_conv2d")
+
+
+@add_arg_scope
 class ConvTranspose2D(Layer):
     """Transposed conv (convolutional.py:747-893); weights [k, k, out, in].
 

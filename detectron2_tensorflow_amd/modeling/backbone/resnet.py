@@ -13,7 +13,8 @@ from contextlib import ExitStack, contextmanager
 import torch
 import torch.nn.functional as F
 
-from ...layers import BatchNorm, Conv2D, Layer, get_norm, ops
+from ...layers import (BatchNorm, Conv2D, DeformConv2D, Layer, ModulatedDeformConv2D, get_norm,
+                       ops)
 from ...layers.activation import is_relu
 from ...layers import initializers as init
 from ...utils.arg_scope import add_arg_scope, arg_scope
@@ -26,8 +27,12 @@ def resnet_arg_scope(freeze, norm):
     with arg_scope([Conv2D], use_bias=False, normalizer=normalizer,
                    normalizer_params={"scope": "norm"}, activation="relu", impl="torch",
                    weights_initializer=init.variance_scaling(2.0, mode="fan_out")), ExitStack() as st:
+        # (DeformConv2D has no impl: it always runs the HIP sampler + the MFMA conv)
+        st.enter_context(arg_scope([DeformConv2D], use_bias=False, normalizer=normalizer,
+                                   normalizer_params={"scope": "norm"}, activation="relu",
+                                   weights_initializer=init.variance_scaling(2.0, mode="fan_out")))
         if freeze:
-            st.enter_context(arg_scope([Conv2D, BatchNorm], trainable=False))
+            st.enter_context(arg_scope([Conv2D, DeformConv2D, BatchNorm], trainable=False))
         yield
 
 
@@ -76,6 +81,50 @@ class BottleneckBlock(Layer):
                 else None)
         h = self.conv1(x, relu_input_sole_consumer=link is not None, grad_from=link, pair_grad=pair)
         h = self.conv2(h, relu_input_sole_consumer=True)
+        return self.conv3(h, residual=sc.contiguous(), final_relu=True,
+                          relu_input_sole_consumer=True, res_grad_to=link)
+
+
+@add_arg_scope
+class DeformBottleneckBlock(Layer):
+    """blocks.py:189-243: the bottleneck whose 3x3 is a DeformConv2D (same
+    scopes: shortcut, conv1, conv2, conv3)."""
+
+    def __init__(self, in_channels, out_channels, bottleneck_channels, stride=1, num_groups=1,
+                 stride_in_1x1=False, rate=1, deform_modulated=False, deform_num_groups=1,
+                 **kwargs):
+        super().__init__(in_channels=in_channels, out_channels=out_channels, **kwargs)
+        self.grad_handoff = False  # set by Stage, as for BottleneckBlock
+        self.grad_pair = True
+        self.shortcut = None
+        if in_channels != out_channels:
+            self.shortcut = Conv2D(in_channels, out_channels, 1, stride=stride, activation=None,
+                                   impl="mfma", scope="shortcut")
+        s1, s3 = (stride, 1) if stride_in_1x1 else (1, stride)
+        self.conv1 = Conv2D(in_channels, bottleneck_channels, 1, stride=s1, impl="mfma",
+                            scope="conv1")
+        op = ModulatedDeformConv2D if deform_modulated else DeformConv2D
+        self.conv2 = op(bottleneck_channels, bottleneck_channels, 3, stride=s3,
+                        num_groups=num_groups, deform_num_groups=deform_num_groups, rate=rate,
+                        scope="conv2")
+        self.conv3 = Conv2D(bottleneck_channels, out_channels, 1, activation=None, impl="mfma",
+                            scope="conv3")
+
+    def call(self, x):
+        # the hand-offs around the block are BottleneckBlock's.  Inside it,
+        # conv1's ReLU output has TWO readers (conv2's offset conv and its
+        # sampler), so conv2 is not declared its sole consumer: conv1 applies
+        # its own ReLU backward to autograd's sum of the two gradients.  conv3
+        # is still the sole consumer of conv2's ReLU output.
+        pair = ({} if self.grad_pair and self.shortcut is not None and torch.is_grad_enabled()
+                else None)
+        if pair is not None:
+            x._d2mi_pair = pair
+        sc = self.shortcut(x, pair_grad=pair) if self.shortcut is not None else x
+        link = ({} if self.grad_handoff and self.shortcut is None and torch.is_grad_enabled()
+                else None)
+        h = self.conv1(x, relu_input_sole_consumer=link is not None, grad_from=link, pair_grad=pair)
+        h = self.conv2(h)
         return self.conv3(h, residual=sc.contiguous(), final_relu=True,
                           relu_input_sole_consumer=True, res_grad_to=link)
 
@@ -153,8 +202,9 @@ class ResNet(Backbone):
         r = cfg.MODEL.RESNETS
         if r.RES5_DILATION not in (1, 2):
             raise ValueError(f"res5_dilation cannot be {r.RES5_DILATION}.")
-        if any(r.DEFORM_ON_PER_STAGE):
-            raise NotImplementedError("deformable ResNet stages are outside the hot path")
+        deform_on = list(r.DEFORM_ON_PER_STAGE)
+        if any(deform_on) and r.DEFORM_MODULATED:
+            ModulatedDeformConv2D()  # raises: the reference class cannot run (layers/convolutional.py)
         super().__init__(**kwargs)
         self._out_features = list(r.OUT_FEATURES)
         freeze_at = cfg.MODEL.BACKBONE.FREEZE_AT
@@ -175,9 +225,14 @@ class ResNet(Backbone):
             first_stride = 1 if (idx == 0 or (stage_idx == 5 and rate == 2)) else 2
             kw = {"in_channels": in_ch, "out_channels": out_ch, "bottleneck_channels": bott,
                   "rate": rate, "num_groups": r.NUM_GROUPS, "stride_in_1x1": r.STRIDE_IN_1X1}
+            block_class = BottleneckBlock
+            if deform_on[idx]:  # (resnet.py:214-218)
+                block_class = DeformBottleneckBlock
+                kw.update(deform_modulated=r.DEFORM_MODULATED,
+                          deform_num_groups=r.DEFORM_NUM_GROUPS)
             name = f"res{stage_idx}"
             with resnet_arg_scope(freeze_at >= stage_idx, r.NORM):
-                self.stages.append(Stage(BottleneckBlock, kw, num_blocks[idx], first_stride,
+                self.stages.append(Stage(block_class, kw, num_blocks[idx], first_stride,
                                          scope=name))
             self.stage_names.append(name)
             stride = int(stride * first_stride)

@@ -202,7 +202,9 @@ class MaskKernelBranch(Layer):
         self.nms_sigma = s.NMS_SIGMA
         self.max_detections_per_image = cfg.TEST.DETECTIONS_PER_IMAGE
         if s.USE_DEFORM_CONV:
-            raise NotImplementedError("deformable convs are outside the hot path (SURVEY section 2)")
+            raise NotImplementedError(
+                "SOLOv2 USE_DEFORM_CONV is not supported: no shipped config sets it, and its "
+                "258-channel first layer is not a multiple of 4 (layers.DeformConv2D needs that)")
         if self.mask_kernel_size != 1:
             raise NotImplementedError("MASK_KERNEL_SIZE > 1 (a KxK dynamic conv) is not shipped "
                                       "by any reference config")

@@ -897,6 +897,40 @@ int d2mi_momentum_sgd_ex(const void* tensor_table, const void* chunk_table, int 
                          float* partial, float clip_norm, float momentum, float lr,
                          const float* lr_dev, void* stream);
 
+/* ------------------------------------------------ Deformable-conv sampling
+ * Replaces the sampling half of DeformConv2D.call (lib/layers/
+ * convolutional.py:410-452: _get_sampling_indices :51-67, the offset add and
+ * clip :422-431, _get_bilinear_interpolatied_pixels :70-115 -- four
+ * tf.gather_nd -- and the reshape / transpose :443-452 into the image that
+ * the k x k / stride-k VALID conv :455-483 reads).
+ * x [N, H, W, C] f32 NHWC, UNPADDED: fix_padding's zero ring (:376) of pb
+ * leading / pe trailing pixels is implied, never materialised (a corner in
+ * the ring reads 0).  offsets: rows of off_stride >= 2*G*k*k floats per
+ * output pixel (n, oh, ow), channel (g*k*k + t)*2 + {0: dy, 1: dx}, t = kh*k +
+ * kw.  cols [N, OH, OW, k*k, C]: the column matrix whose product with
+ * weights.reshape(k*k*C, Cout) is that conv.  OH = (H + pb + pe - k_eff) /
+ * stride + 1 with k_eff = k + (k-1)(rate-1).  Positions, corner clipping and
+ * the weights from the clipped corners follow the reference term by term
+ * (f32, un-contracted).  k in {1, 3}; C % G == 0; (C/G) % 4 == 0; stride,
+ * rate >= 1; x / cols 16-byte aligned. */
+int d2mi_deform_sample_fwd(const float* x, const float* offsets, int N, int H, int W, int C,
+                           int G, int k, int stride, int rate, int pb, int pe, int off_stride,
+                           float* cols, void* stream);
+/* Gradient of the above as TF autodiff forms it for convolutional.py:410-452
+ * (floor passes nothing, clip_by_value passes inside [0, Hp-1], the clipped
+ * corner floats are constants; gather_nd's gradient is a scatter-add).
+ * gcols [N, OH, OW, k*k, C].  gx [N, H, W, C] (nullable): every element
+ * written, no float atomics, bitwise reproducible (sorted destination keys,
+ * fixed-order sums).  goffsets (nullable): rows of goff_stride floats, the
+ * first 2*G*k*k as `offsets`, the rest (up to 16) written 0.  ws: at least
+ * d2mi_deform_sample_bwd_workspace_size bytes (0 for a bad shape). */
+size_t d2mi_deform_sample_bwd_workspace_size(int N, int H, int W, int C, int G, int k, int stride,
+                                             int rate, int pb, int pe);
+int d2mi_deform_sample_bwd(const float* x, const float* offsets, const float* gcols, int N, int H,
+                           int W, int C, int G, int k, int stride, int rate, int pb, int pe,
+                           int off_stride, int goff_stride, float* gx, float* goffsets, void* ws,
+                           size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,11 +1,13 @@
 """Per-kernel micro-benchmarks of the hot path on the MI355X (HIP-event timing).
 
-    python tools/bench_kernels.py [--only conv,roi,nms,topk] [--iters 20]
+    python tools/bench_kernels.py [--only conv,roi,nms,topk,deform] [--iters 20]
 
 conv: the MFMA implicit-GEMM kernel vs torch/MIOpen conv2d (channels_last) on
 the FPN / RPN / mask-head / backbone shapes of Mask R-CNN R50-FPN at 1333x800
 (batch 2), in TFLOP/s of algorithmic flops.  roi: multi-level ROIAlign in
-algorithmic GB/s.  nms/topk: microseconds per call.
+algorithmic GB/s.  nms/topk: microseconds per call.  deform: the deformable-conv
+sampler, forward and backward, at the res3..res5 shapes of the dconv configs,
+in microseconds and as a fraction of 8 TB/s on the least bytes.
 """
 import argparse
 import json
@@ -206,6 +208,54 @@ def bench_topk(dev, iters):
     return out
 
 
+DEFORM_SHAPES = [("res3", 2, 100, 168, 128), ("res4", 2, 50, 84, 256), ("res5", 2, 25, 42, 512)]
+HBM_BPS = 8e12
+
+
+def bench_deform(dev, iters):
+    """ops.deform_sample forward / backward, k 3, G 1, stride 1, SAME.  Offsets
+    (a) "model": a random-init layer's own offset conv over a ReLU feature
+    map, its weights scaled once so that the offsets have unit std (a fresh
+    layer's are all 0) -- smooth in space, as learned ones are; (b) iid
+    normal(0, 2).  Least bytes: fwd x + offsets read, cols written; bwd gcols
+    + x + offsets read, gx + goffsets written.  bwd_gx_us / bwd_goff_us: the
+    two halves alone (key emit + sort + sum pass; the offset-gradient gather)."""
+    from detectron2_tensorflow_amd.layers import DeformConv2D
+    out = []
+    for name, N, H, W, C in DEFORM_SHAPES:
+        g = torch.Generator(device="cpu").manual_seed(H)
+        x = torch.relu(torch.randn(N, H, W, C, generator=g)).to(dev)
+        gcols = torch.randn(N, H, W, 9 * C, generator=g).to(dev)
+        layer = DeformConv2D(C, C, 3).to(dev)
+        with torch.no_grad():
+            layer.offset_weights.copy_(torch.randn(3, 3, C, 18, generator=g))
+            std = layer._offsets(x, (1, 1))[..., :18].std()
+            layer.offset_weights.div_(std)
+            model_off = layer._offsets(x, (1, 1)).contiguous()
+        rand_off = (2.0 * torch.randn(N, H, W, 18, generator=g)).to(dev)
+        for kind, off in (("model", model_off), ("normal(0,2)", rand_off)):
+            args = (3, 1, 1, (1, 1), 1)
+            with torch.no_grad():
+                fwd = timeit(lambda: ops.deform_sample(x, off, *args), iters)
+            bwd = timeit(lambda: ops.deform_sample_bwd(x, off, gcols, *args), iters)
+            bwd_x = timeit(lambda: ops.deform_sample_bwd(x, off, gcols, *args, want_offsets=False),
+                           iters)
+            bwd_o = timeit(lambda: ops.deform_sample_bwd(x, off, gcols, *args, want_x=False), iters)
+            offb = 4.0 * N * H * W * 18
+            fb = 4.0 * (x.numel() + gcols.numel()) + offb
+            bb = 4.0 * (gcols.numel() + 2 * x.numel()) + 3 * offb
+            clipped = float(((off[..., 0:18:2].abs() > 1) | (off[..., 1:18:2].abs() > 1)).float().mean())
+            out.append({"kernel": "deform_sample", "shape": f"{name} {N}x{H}x{W}x{C}",
+                        "offsets": kind, "offset_std": round(float(off[..., :18].std()), 3),
+                        "fwd_us": round(fwd * 1e3, 1),
+                        "fwd_frac_8TBps": round(fb / (fwd * 1e-3) / HBM_BPS, 3),
+                        "bwd_us": round(bwd * 1e3, 1),
+                        "bwd_frac_8TBps": round(bb / (bwd * 1e-3) / HBM_BPS, 3),
+                        "bwd_gx_us": round(bwd_x * 1e3, 1), "bwd_goff_us": round(bwd_o * 1e3, 1),
+                        "frac_offsets_over_1px": round(clipped, 3)})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="conv,wgrad,roi,paste,nms,topk")
@@ -220,7 +270,7 @@ def main():
     dev = torch.device("cuda:0")
     fns = {"conv": bench_conv, "wgrad": bench_wgrad, "roi": bench_roi, "paste": bench_paste,
            "nms": bench_nms,
-           "topk": bench_topk}
+           "topk": bench_topk, "deform": bench_deform}
     for name in a.only.split(","):
         for row in fns[name](dev, a.iters):
             print(json.dumps(row), flush=True)
