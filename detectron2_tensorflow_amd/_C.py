@@ -8,8 +8,11 @@ device pointers and ``hipStream_t`` handles are passed straight from torch.
 """
 import ctypes
 import os
+import re
 
 import torch
+
+from . import _build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # D2MI_LIB: an alternative build of the same library (A/B kernel experiments)
@@ -22,152 +25,38 @@ c_int, c_float, c_size_t, c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_size
 c_char_p = ctypes.c_char_p
 P = c_void_p  # device or host pointer
 
-# name -> (restype, argtypes)
-_SIGS = {
-    "d2mi_version": (c_int, []),
-    "d2mi_source_hash": (c_char_p, []),
-    "d2mi_set_tuning": (c_int, [c_char_p, c_int]),
-    "d2mi_get_tuning": (c_int, [c_char_p]),
-    "d2mi_last_error": (c_char_p, []),
-    "d2mi_error_word_dev": (c_void_p, []),
-    "d2mi_clear_errors": (c_int, [P]),
-    "d2mi_graph_census": (c_int, [P, P, c_int]),
-    "d2mi_capture_census": (c_int, [P, P, c_int]),
-    "d2mi_roi_align_fwd": (c_int, [P, P, P, c_int, c_int, P, P, c_int, c_int, c_int, c_int, c_int,
-                                   c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
-    "d2mi_roi_align_bwd_workspace_size": (c_size_t, [P, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "d2mi_roi_align_bwd": (c_int, [P, P, P, c_int, c_int, P, P, c_int, c_int, c_int, c_int, c_int,
-                                   c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
-    "d2mi_roi_align_bwd_ex": (c_int, [P, P, P, c_int, c_int, P, P, c_int, c_int, c_int, c_int,
-                                      c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int,
-                                      P, c_size_t, P]),
-    "d2mi_roi_align_bwd2_workspace_size": (c_size_t, [P, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                   c_int, c_int, c_int, c_int]),
-    "d2mi_roi_align_bwd2": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                    c_int, c_int, P, P, c_int, c_int, c_int, c_int, P, P, P, c_int,
-                                    c_int, c_int, c_int, P, c_int, P, c_size_t, P]),
-    "d2mi_roi_align_bwd2_ex": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                       c_int, c_int, P, P, c_int, c_int, c_int, c_int, P, P, P,
-                                       c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int,
-                                       P, c_size_t, P]),
-    "d2mi_nms_workspace_size": (c_size_t, [c_int, c_int]),
-    "d2mi_nms": (c_int, [P, P, P, c_int, c_int, c_int, c_float, P, P, P, c_size_t, P]),
-    "d2mi_topk_workspace_size": (c_size_t, [c_int, c_int]),
-    "d2mi_topk": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
-    "d2mi_subsample_workspace_size": (c_size_t, [c_int, c_int]),
-    "d2mi_subsample": (c_int, [P, c_int, c_int, ctypes.c_longlong, c_int, c_int, P, P, P, P, P,
-                               c_int, P, c_size_t, P]),
-    "d2mi_grid_anchors": (c_int, [c_int, c_int, c_float, P, c_int, P, P]),
-    "d2mi_apply_deltas": (c_int, [P, P, c_int, c_int, P, c_float, P, P]),
-    "d2mi_rpn_proposals_workspace_size": (c_size_t, [c_int, c_int, P, c_int, c_int, c_int]),
-    "d2mi_rpn_proposals": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, c_int, c_int, c_float,
-                                   c_float, P, c_float, P, P, P, P, c_size_t, P]),
-    "d2mi_rpn_proposals_ex": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, P, c_int, c_int,
-                                      c_float, c_float, P, c_float, P, P, P, P, c_size_t, P]),
-    "d2mi_rpn_head_gather": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P]),
-    "d2mi_rpn_head_scatter": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P]),
-    "d2mi_fast_rcnn_workspace_size": (c_size_t, [c_int, c_int, c_int, c_float, c_int]),
-    "d2mi_fast_rcnn_inference": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P,
-                                         c_float, c_float, c_float, c_int, P, P, P, P, P, P,
-                                         c_size_t, P]),
-    "d2mi_retinanet_workspace_size": (c_size_t, [c_int, c_int, P, c_int, c_int, c_int]),
-    "d2mi_retinanet_inference": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float,
-                                         c_float, c_int, P, c_float, P, P, P, P, P, c_size_t, P]),
-    "d2mi_matrix_nms_workspace_size": (c_size_t, [c_int]),
-    "d2mi_matrix_nms": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, P, P, c_size_t, P]),
-    "d2mi_resize_bilinear": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P,
-                                     P]),
-    "d2mi_solo_cells": (c_int, [P, P, c_int, c_int, c_int, c_float, P, P, P, P, P]),
-    "d2mi_solo_mask_stats": (c_int, [P, c_int, c_int, c_float, P, P, P]),
-    "d2mi_solo_select_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "d2mi_solo_select": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float,
-                                 c_float, c_int, P, P, P, P, P, P, c_size_t, P]),
-    "d2mi_solo_matrix_nms_workspace_size": (c_size_t, [c_int, c_int]),
-    "d2mi_solo_matrix_nms": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, P,
-                                     c_size_t, P]),
-    "d2mi_solo_finalize_workspace_size": (c_size_t, [c_int, c_int, c_int]),
-    "d2mi_solo_finalize": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_int,
-                                   c_float, c_int, c_int, P, P, P, P, P, P, c_size_t, P]),
-    "d2mi_group_norm_workspace_size": (c_size_t, [c_int] * 5),
-    "d2mi_group_norm_nhwc": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, c_int,
-                                     c_int, c_int, P, P, c_size_t, P]),
-    "d2mi_group_norm_levels_workspace_size": (c_size_t, [P, c_int, c_int, c_int]),
-    "d2mi_group_norm_nhwc_levels": (c_int, [P, P, c_int, c_int, c_int, P, P, c_float, c_int, P, P,
-                                            c_size_t, P]),
-    "d2mi_conv_pack_weights": (c_int, [P, c_int, c_int, c_int, c_int, P, P]),
-    "d2mi_conv_pack_weights_many": (c_int, [c_int, P, P, P, P]),
-    "d2mi_conv2d_nhwc": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
-                                 c_int, c_int, c_int, c_int, c_int, P]),
-    "d2mi_conv2d_workspace_size": (c_size_t, [c_int] * 10),
-    "d2mi_conv2d_wgrad_workspace_size": (c_size_t, [c_int] * 10),
-    "d2mi_fold_frozen_bn": (c_int, [P, P, P, P, P, P, c_float, c_int, c_int, c_int, c_int, P, P,
-                                    P, P]),
-    "d2mi_fold_frozen_bn_bwd_workspace_size": (c_size_t, [c_int]),
-    "d2mi_fold_frozen_bn_bwd": (c_int, [P, P, P, P, P, P, P, c_float, c_int, c_int, c_int, c_int,
-                                        P, P, P, P, P, c_size_t, P]),
-    "d2mi_conv2d_wgrad": (c_int, [P, P, P, P] + [c_int] * 10 + [P, c_size_t, P]),
-    "d2mi_conv2d_wgrad_ex": (c_int, [P, P, P, P] + [c_int] * 11 + [P, c_size_t, P]),
-    "d2mi_conv2d_nhwc_ex": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
-                                    c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
-    "d2mi_conv2d_nhwc_gated": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int,
-                                       c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
-    "d2mi_conv2d_levels_workspace_size": (c_size_t, [P, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                  c_int, c_int]),
-    "d2mi_conv2d_nhwc_levels": (c_int, [P, P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int,
-                                        c_int, c_int, c_int, P, c_size_t, P]),
-    "d2mi_split_bf16x3": (c_int, [P, ctypes.c_int64, P, P]),
-    "d2mi_paste_masks": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P]),
-    "d2mi_wgrad_skinny_workspace_size": (c_size_t, [c_int, c_int, c_int]),
-    "d2mi_wgrad_skinny": (c_int, [P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
-    "d2mi_wgrad_skinny_ex": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, P, c_size_t, P]),
-    "d2mi_wgrad_skinny_levels_workspace_size": (c_size_t, [P, c_int, c_int, c_int]),
-    "d2mi_wgrad_skinny_levels": (c_int, [P, P, P, c_int, c_int, c_int, P, P, c_int, P, c_size_t,
-                                         P]),
-    "d2mi_column_sum_workspace_size": (c_size_t, [ctypes.c_longlong, c_int]),
-    "d2mi_column_sum": (c_int, [P, ctypes.c_longlong, c_int, P, P, c_size_t, P]),
-    "d2mi_upsample2x_grad": (c_int, [P, c_int, c_int, c_int, c_int, P, P]),
-    "d2mi_stride_scatter": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
-    "d2mi_stride_scatter_ex": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
-    "d2mi_match_workspace_size": (c_size_t, [c_int, c_int]),
-    "d2mi_match_boxes": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, c_int, c_int, c_float,
-                                 c_float, P, P, P, c_size_t, P]),
-    "d2mi_match_boxes_ex": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, c_int, c_int,
-                                    c_float, c_float, P, P, P, c_size_t, P]),
-    "d2mi_stem_pool": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),
-    "d2mi_stem_conv": (c_int, [P, P, c_int, c_int, c_int, P, P]),
-    "d2mi_preprocess_images": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
-    "d2mi_roi_gt_classes": (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, c_int, P, P]),
-    "d2mi_roi_sample_take": (c_int, [P, P, P, P, P, P] + [c_int] * 6 + [P] * 13),
-    "d2mi_rpn_loss_blocks": (c_int, []),
-    "d2mi_rpn_loss_fwd": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, P, c_float, P, P]),
-    "d2mi_rpn_loss_bwd": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, P, c_float, P, P, P,
-                                  P]),
-    "d2mi_rpn_loss_bwd_ex": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, P, c_float, P, P,
-                                     c_float, P, P, P]),
-    "d2mi_fast_rcnn_loss_workspace_size": (c_size_t, [c_int]),
-    "d2mi_fast_rcnn_loss_fwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P, c_float, P, P,
-                                        c_size_t, P]),
-    "d2mi_fast_rcnn_loss_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P, c_float, P, P,
-                                        P, P, P]),
-    "d2mi_mask_loss_workspace_size": (c_size_t, [c_int]),
-    "d2mi_mask_loss_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, c_size_t, P]),
-    "d2mi_mask_loss_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, P, P]),
-    "d2mi_sgd_table_sizes": (c_int, [P, P, P]),
-    "d2mi_momentum_sgd": (c_int, [P, P, c_int, P, c_float, c_float, c_float, P]),
-    "d2mi_momentum_sgd_ex": (c_int, [P, P, c_int, P, c_float, c_float, c_float, P, P]),
-    "d2mi_retina_loss_blocks": (c_int, []),
-    "d2mi_retina_loss_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P,
-                                     c_float, c_float, c_float, P, P, P]),
-    "d2mi_retina_loss_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, c_int, P,
-                                     P, c_float, c_float, c_float, P, P, P, P]),
-    "d2mi_fold_many_sizes": (c_int, [P, P]),
-    "d2mi_fold_frozen_bn_many": (c_int, [P, c_int, c_int, P]),
-    "d2mi_fold_frozen_bn_bwd_many": (c_int, [P, c_int, c_int, c_int, P, P]),
-    "d2mi_deform_sample_fwd": (c_int, [P, P] + [c_int] * 11 + [P, P]),
-    "d2mi_deform_sample_bwd_workspace_size": (c_size_t, [c_int] * 10),
-    "d2mi_deform_sample_bwd": (c_int, [P, P, P] + [c_int] * 12 + [P, P, P, c_size_t, P]),
-}
+_SCALARS = {"int": c_int, "float": c_float, "size_t": c_size_t,
+            "long long": ctypes.c_longlong, "int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32}
+_DECL = re.compile(r"([\w\s\*]+?)\b(d2mi_\w+)\s*\(([^()]*)\)\s*;")
 
+
+def _ctype(decl, named):
+    """ctypes class of a C return type, or of a parameter (``named``)."""
+    t = " ".join(decl.replace("*", " * ").split())
+    if "*" in t or "[" in t:
+        return c_char_p if re.fullmatch(r"const char \*( \w+)?", t) else c_void_p
+    words = [w for w in t.split() if w != "const"]
+    scalar = " ".join(words[:-1] if named else words)
+    if scalar not in _SCALARS:  # fail closed: never guess a width
+        raise TypeError(f"d2mi.h: no ctypes mapping for {decl.strip()!r}")
+    return _SCALARS[scalar]
+
+
+def parse_header(src):
+    """name -> (restype, argtypes) of every ``ret d2mi_name(params);`` in the
+    text of include/d2mi.h: the header is the only statement of the ABI."""
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+    sigs = {}
+    for ret, name, params in _DECL.findall(src):
+        params = params.strip()
+        args = [] if params == "void" else [_ctype(p, True) for p in params.split(",")]
+        sigs[name] = (_ctype(ret, False), args)
+    return sigs
+
+
+with open(os.path.join(_build.INCLUDE, "d2mi.h")) as _f:
+    _SIGS = parse_header(_f.read())  # the tree's header, also under D2MI_LIB
 EXPORTED = tuple(_SIGS)
 
 
@@ -190,7 +79,6 @@ def load(path=LIB_PATH):
         fn.argtypes = args
     # the library must be built from the sources next to it (a stale prebuilt
     # .so would silently run other kernels than the tree's)
-    from . import _build
     if os.path.isdir(_build.CSRC) and os.environ.get("D2MI_LIB") is None:
         want, got = _build.source_hash(), lib.d2mi_source_hash().decode()
         if got != want:

@@ -59,15 +59,27 @@ struct Workspace {
   bool ok() const { return off <= cap; }
 };
 
-// Sizing twin of Workspace (same alignment rule) for *_workspace_size().
+// Sizing twin of Workspace (same alignment rule, null pointers): a layout
+// written once as a template over the allocator is carved over a Workspace
+// by the op and measured over a WorkspaceSizer by its *_workspace_size().
 struct WorkspaceSizer {
   size_t off = 0;
   template <typename T>
-  void take(size_t n) {
+  T* take(size_t n) {
     off = align_up(off, 256);
     off += n * sizeof(T);
+    return nullptr;
   }
 };
+
+// Bytes of a layout struct L { template <typename A> void lay(A&, args...); }.
+template <typename L, typename... Args>
+size_t layout_bytes(const Args&... args) {
+  L l;
+  WorkspaceSizer z;
+  l.lay(z, args...);
+  return z.off;
+}
 
 // float -> uint32 whose unsigned order equals the float order.  -0.0 maps to
 // +0.0's word: TF's top_k / NMS compare the values, so the two zeros tie (and
@@ -136,6 +148,28 @@ __device__ __forceinline__ float4 apply_delta(float4 box, float4 d, float wy, fl
 __device__ __forceinline__ float4 clip_box(float4 b, float hmax, float wmax) {
   return make_float4(fmaxf(fminf(b.x, hmax), 0.f), fmaxf(fminf(b.y, wmax), 0.f),
                      fmaxf(fminf(b.z, hmax), 0.f), fmaxf(fminf(b.w, wmax), 0.f));
+}
+
+// Exact 3-term bf16 split of four floats (h + m + l == x, truncation): the
+// precision contract of every split conv (conv_mfma.hip's header).
+// Each output packs 4 bf16 (element order = float4 order).
+__device__ __forceinline__ void split3(const float4 v, uint2& h, uint2& m, uint2& l) {
+  const float x[4] = {v.x, v.y, v.z, v.w};
+  uint32_t hb[4], mb[4], lb[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    hb[e] = __float_as_uint(x[e]) & 0xffff0000u;
+    const float r = x[e] - __uint_as_float(hb[e]);
+    mb[e] = __float_as_uint(r) & 0xffff0000u;
+    lb[e] = __float_as_uint(r - __uint_as_float(mb[e]));
+  }
+  // each pair packed by one byte permute (the high halves of two words)
+  h.x = __builtin_amdgcn_perm(hb[1], hb[0], 0x07060302u);
+  h.y = __builtin_amdgcn_perm(hb[3], hb[2], 0x07060302u);
+  m.x = __builtin_amdgcn_perm(mb[1], mb[0], 0x07060302u);
+  m.y = __builtin_amdgcn_perm(mb[3], mb[2], 0x07060302u);
+  l.x = __builtin_amdgcn_perm(lb[1], lb[0], 0x07060302u);
+  l.y = __builtin_amdgcn_perm(lb[3], lb[2], 0x07060302u);
 }
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }

@@ -97,27 +97,6 @@ constexpr int kAblate = D2MI_CONV_ABLATE;
 // since r4 (was the runtime D2MI_CONV_PRIO).
 constexpr bool kPrioMfma = true;
 
-// Exact 3-term bf16 split of four floats (truncation; see the header).
-// Each output packs 4 bf16 (element order = float4 order).
-__device__ __forceinline__ void split3(const float4 v, uint2& h, uint2& m, uint2& l) {
-  const float x[4] = {v.x, v.y, v.z, v.w};
-  uint32_t hb[4], mb[4], lb[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    hb[e] = __float_as_uint(x[e]) & 0xffff0000u;
-    const float r = x[e] - __uint_as_float(hb[e]);
-    mb[e] = __float_as_uint(r) & 0xffff0000u;
-    lb[e] = __float_as_uint(r - __uint_as_float(mb[e]));
-  }
-  // each pair packed by one byte permute (the high halves of two words)
-  h.x = __builtin_amdgcn_perm(hb[1], hb[0], 0x07060302u);
-  h.y = __builtin_amdgcn_perm(hb[3], hb[2], 0x07060302u);
-  m.x = __builtin_amdgcn_perm(mb[1], mb[0], 0x07060302u);
-  m.y = __builtin_amdgcn_perm(mb[3], mb[2], 0x07060302u);
-  l.x = __builtin_amdgcn_perm(lb[1], lb[0], 0x07060302u);
-  l.y = __builtin_amdgcn_perm(lb[3], lb[2], 0x07060302u);
-}
-
 struct ConvArgs {
   const float* x;
   const float* w;  // [KH][KW][Cout][Cin]

@@ -287,25 +287,6 @@ __device__ __forceinline__ int wswz(int row, int elem) {
   return row * LDW + ((((elem >> 3) ^ (row >> 2)) & 3) << 3) + (elem & 7);
 }
 
-__device__ __forceinline__ void split3w(const float4 v, uint2& h, uint2& m, uint2& l) {
-  const float x[4] = {v.x, v.y, v.z, v.w};
-  uint32_t hb[4], mb[4], lb[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    hb[e] = __float_as_uint(x[e]) & 0xffff0000u;
-    const float r = x[e] - __uint_as_float(hb[e]);
-    mb[e] = __float_as_uint(r) & 0xffff0000u;
-    lb[e] = __float_as_uint(r - __uint_as_float(mb[e]));
-  }
-  // each pair packed by one byte permute (the high halves of two words)
-  h.x = __builtin_amdgcn_perm(hb[1], hb[0], 0x07060302u);
-  h.y = __builtin_amdgcn_perm(hb[3], hb[2], 0x07060302u);
-  m.x = __builtin_amdgcn_perm(mb[1], mb[0], 0x07060302u);
-  m.y = __builtin_amdgcn_perm(mb[3], mb[2], 0x07060302u);
-  l.x = __builtin_amdgcn_perm(lb[1], lb[0], 0x07060302u);
-  l.y = __builtin_amdgcn_perm(lb[3], lb[2], 0x07060302u);
-}
-
 // n / d for 0 <= n < 2^31 by multiply-high (Granlund-Montgomery).
 struct FastDiv {
   uint32_t d, m, l;
@@ -378,7 +359,7 @@ __global__ __launch_bounds__(256, OCC) void conv_wgrad_split_kernel(WgradArgs a,
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         uint2 h, m, l;
-        split3w(make_float4(f[j], f[4 + j], f[8 + j], f[12 + j]), h, m, l);
+        split3(make_float4(f[j], f[4 + j], f[8 + j], f[12 + j]), h, m, l);
         const int o = wswz(4 * cga + j, 4 * pga);
         *reinterpret_cast<uint2*>(&As[o]) = h;
         *reinterpret_cast<uint2*>(&As[BM * LDW + o]) = m;
@@ -392,7 +373,7 @@ __global__ __launch_bounds__(256, OCC) void conv_wgrad_split_kernel(WgradArgs a,
         const float4 v = make_float4(f[j], f[4 + j], f[8 + j], f[12 + j]);
         if (do_bias) bsum[j] += ((v.x + v.y) + v.z) + v.w;
         uint2 h, m, l;
-        split3w(v, h, m, l);
+        split3(v, h, m, l);
         const int o = wswz(4 * cgb + j, 4 * pgb);
         *reinterpret_cast<uint2*>(&Bs[o]) = h;
         *reinterpret_cast<uint2*>(&Bs[BN * LDW + o]) = m;
@@ -616,7 +597,7 @@ __global__ __launch_bounds__(1024, 1) void conv_wgrad_ws_kernel(WgradArgs a, Fas
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         uint2 h, m, l;
-        split3w(make_float4(f[j], f[4 + j], f[8 + j], f[12 + j]), h, m, l);
+        split3(make_float4(f[j], f[4 + j], f[8 + j], f[12 + j]), h, m, l);
         const int o = wswz(4 * cga + j, 4 * pga);
         *reinterpret_cast<uint2*>(&As[o]) = h;
         *reinterpret_cast<uint2*>(&As[BM * LDW + o]) = m;
@@ -629,7 +610,7 @@ __global__ __launch_bounds__(1024, 1) void conv_wgrad_ws_kernel(WgradArgs a, Fas
           const float4 v = make_float4(g[j], g[4 + j], g[8 + j], g[12 + j]);
           if (do_bias) bsum[j] += ((v.x + v.y) + v.z) + v.w;
           uint2 h, m, l;
-          split3w(v, h, m, l);
+          split3(v, h, m, l);
           const int o = wswz(4 * cgb + j, 4 * pgb);
           *reinterpret_cast<uint2*>(&Bs[o]) = h;
           *reinterpret_cast<uint2*>(&Bs[BN * LDW + o]) = m;

@@ -465,36 +465,25 @@ int make_args(DeformArgs* a, int N, int H, int W, int C, int G, int k, int strid
   return 0;
 }
 
-struct BwdSpace {
-  uint64_t* keys[2];  // ping-pong
-  int32_t* hist;      // [bins][tiles] + the digit totals
-  int32_t* start;     // [destinations + 1]
-};
-
 size_t key_count(const DeformArgs& a) { return (size_t)a.N * a.OH * a.OW * a.G * a.KK * 4; }
 
 size_t hist_count(size_t cap) {
   return (size_t)kRadixMaxBins * ((cap + kRadixTile - 1) / kRadixTile + 1);  // + the digit totals
 }
 
-// the sizing twin of carve() below: same takes, same order
-size_t bwd_space_bytes(const DeformArgs& a) {
-  const size_t cap = key_count(a);
-  WorkspaceSizer z;
-  z.take<uint64_t>(cap);
-  z.take<uint64_t>(cap);
-  z.take<int32_t>(hist_count(cap));
-  z.take<int32_t>((size_t)a.N * a.H * a.W * a.G + 1);
-  return z.off;
-}
-
-void carve(Workspace& w, const DeformArgs& a, BwdSpace* s) {
-  const size_t cap = key_count(a);
-  s->keys[0] = w.take<uint64_t>(cap);
-  s->keys[1] = w.take<uint64_t>(cap);
-  s->hist = w.take<int32_t>(hist_count(cap));
-  s->start = w.take<int32_t>((size_t)a.N * a.H * a.W * a.G + 1);
-}
+struct BwdSpace {
+  uint64_t* keys[2];  // ping-pong
+  int32_t* hist;      // [bins][tiles] + the digit totals
+  int32_t* start;     // [destinations + 1]
+  template <typename A>
+  void lay(A& w, const DeformArgs& a) {
+    const size_t cap = key_count(a);
+    keys[0] = w.template take<uint64_t>(cap);
+    keys[1] = w.template take<uint64_t>(cap);
+    hist = w.template take<int32_t>(hist_count(cap));
+    start = w.template take<int32_t>((size_t)a.N * a.H * a.W * a.G + 1);
+  }
+};
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -521,7 +510,7 @@ extern "C" size_t d2mi_deform_sample_bwd_workspace_size(int N, int H, int W, int
                                                         int stride, int rate, int pb, int pe) {
   DeformArgs a;
   if (make_args(&a, N, H, W, C, G, k, stride, rate, pb, pe, 2 * G * k * k)) return 0;
-  return bwd_space_bytes(a);
+  return layout_bytes<BwdSpace>(a);
 }
 
 extern "C" int d2mi_deform_sample_bwd(const float* x, const float* offsets, const float* gcols,
@@ -548,7 +537,7 @@ extern "C" int d2mi_deform_sample_bwd(const float* x, const float* offsets, cons
   if (!gx) return 0;
   Workspace w(ws, ws_bytes);
   BwdSpace s;
-  carve(w, a, &s);
+  s.lay(w, a);
   D2MI_REQUIRE(ws && w.ok(), "deform_sample_bwd: workspace too small (%zu < %zu)", ws_bytes, w.off);
   hipLaunchKernelGGL(deform_emit_kernel, dim3((items + 255) / 256), dim3(256), 0, st, offsets, a,
                      items, s.keys[0]);

@@ -301,6 +301,17 @@ static int gn_levels_plan(const int32_t* dims, int nlev, int C, int G, GnLevels&
   return 0;
 }
 
+// n_partial per-chunk group sums, n_stats means and variances (both ops)
+struct GnSpace {
+  float *partial, *mean, *var;
+  template <typename A>
+  void lay(A& a, size_t n_partial, size_t n_stats) {
+    partial = a.template take<float>(n_partial);
+    mean = a.template take<float>(n_stats);
+    var = a.template take<float>(n_stats);
+  }
+};
+
 }  // namespace
 }  // namespace d2mi
 
@@ -309,11 +320,7 @@ using namespace d2mi;
 extern "C" size_t d2mi_group_norm_workspace_size(int N, int H, int W, int C, int G) {
   int cp;
   const int chunks = gn_chunks(H * W, cp);
-  WorkspaceSizer z;
-  z.take<float>((size_t)N * chunks * G);
-  z.take<float>((size_t)N * G);
-  z.take<float>((size_t)N * G);
-  return z.off;
+  return layout_bytes<GnSpace>((size_t)N * chunks * G, (size_t)N * G);
 }
 
 extern "C" int d2mi_group_norm_nhwc(const float* x, int N, int H, int W, int C, int G,
@@ -333,9 +340,9 @@ extern "C" int d2mi_group_norm_nhwc(const float* x, int N, int H, int W, int C, 
   const int HW = H * W;
   const int chunks = gn_chunks(HW, chunk_px);
   Workspace w(workspace, workspace_bytes);
-  float* partial = w.take<float>((size_t)N * chunks * G);
-  float* mean = w.take<float>((size_t)N * G);
-  float* var = w.take<float>((size_t)N * G);
+  GnSpace o;
+  o.lay(w, (size_t)N * chunks * G, (size_t)N * G);
+  float *partial = o.partial, *mean = o.mean, *var = o.var;
   D2MI_REQUIRE(w.ok(), "GroupNorm workspace too small (%zu < %zu)", workspace_bytes, w.off);
   const float inv_count = 1.f / (float)((size_t)HW * (C / G));
   hipLaunchKernelGGL(gn_sum_kernel, dim3(chunks, N), dim3(kGnThreads), 0, st, x, HW, C, G,
@@ -372,11 +379,7 @@ extern "C" size_t d2mi_group_norm_levels_workspace_size(const int32_t* dims, int
   GnLevels lv;
   size_t np = 0, ns = 0;
   if (gn_levels_plan(dims, nlev, C, G, lv, np, ns)) return 0;
-  WorkspaceSizer z;
-  z.take<float>(np);
-  z.take<float>(ns);
-  z.take<float>(ns);
-  return z.off;
+  return layout_bytes<GnSpace>(np, ns);
 }
 
 extern "C" int d2mi_group_norm_nhwc_levels(const float* const* xs, const int32_t* dims, int nlev,
@@ -402,9 +405,9 @@ extern "C" int d2mi_group_norm_nhwc_levels(const float* const* xs, const int32_t
   if (lv.wg0[nlev] == 0) return 0;
   hipStream_t st = as_stream(stream);
   Workspace w(workspace, workspace_bytes);
-  float* partial = w.take<float>(np);
-  float* mean = w.take<float>(ns);
-  float* var = w.take<float>(ns);
+  GnSpace o;
+  o.lay(w, np, ns);
+  float *partial = o.partial, *mean = o.mean, *var = o.var;
   D2MI_REQUIRE(w.ok(), "GroupNorm workspace too small (%zu < %zu)", workspace_bytes, w.off);
   hipLaunchKernelGGL(gn_sum_levels_kernel, dim3(lv.wg0[nlev]), dim3(kGnThreads), 0, st, lv, C, G,
                      nullptr, partial);

@@ -84,18 +84,22 @@ __global__ __launch_bounds__(256) void decay_kernel(const float* inter, const fl
   if (threadIdx.x == 0) out[j] = scores[j] * red[0];
 }
 
+struct MnmsSpace {
+  float *inter, *sums, *comp;
+  template <typename A>
+  void lay(A& a, int M) {
+    inter = a.template take<float>((size_t)M * M);
+    sums = a.template take<float>(M);
+    comp = a.template take<float>(M);
+  }
+};
+
 }  // namespace
 }  // namespace d2mi
 
 using namespace d2mi;
 
-extern "C" size_t d2mi_matrix_nms_workspace_size(int M) {
-  WorkspaceSizer z;
-  z.take<float>((size_t)M * M);
-  z.take<float>(M);
-  z.take<float>(M);
-  return z.off;
-}
+extern "C" size_t d2mi_matrix_nms_workspace_size(int M) { return layout_bytes<MnmsSpace>(M); }
 
 extern "C" int d2mi_matrix_nms(const float* masks, const int64_t* classes, const float* scores,
                                const float* sum_masks, int M, int HW, int kernel, float sigma,
@@ -107,9 +111,9 @@ extern "C" int d2mi_matrix_nms(const float* masks, const int64_t* classes, const
   if (M == 0) return 0;
   hipStream_t st = as_stream(stream);
   Workspace w(workspace, workspace_bytes);
-  float* inter = w.take<float>((size_t)M * M);
-  float* sums = w.take<float>(M);
-  float* comp = w.take<float>(M);
+  MnmsSpace o;
+  o.lay(w, M);
+  float *inter = o.inter, *sums = o.sums, *comp = o.comp;
   D2MI_REQUIRE(w.ok(), "matrix_nms workspace too small (%zu < %zu)", workspace_bytes, w.off);
   // inter = masks . masks^T : a 1x1 conv over M "pixels" with Cin = HW, Cout = M,
   // whose packed [Cout][Cin] weight is the mask matrix itself.

@@ -367,15 +367,35 @@ __global__ __launch_bounds__(64 * (1 + 2 * kFpProp)) void nms_scan_fp_kernel(
   if (threadIdx.x == 0) num_keep[s] = kept;
 }
 
+struct SortedSpace {
+  uint64_t *mask, *colw;
+  template <typename A>
+  void lay(A& a, int S, int cap) {
+    const int T = (cap + 63) / 64;
+    mask = a.template take<uint64_t>((size_t)S * cap * T);
+    // column words (the fixed-point scan)
+    colw = a.template take<uint64_t>((size_t)S * T * 2 * 64);
+  }
+};
+
+// d2mi_nms: the keys and lengths its own kernel writes, then nms_core's space
+struct NmsSpace {
+  uint64_t* keys;
+  int32_t* lens;
+  void* core_ws;
+  size_t core_bytes;
+  template <typename A>
+  void lay(A& a, int S, int cap) {
+    keys = a.template take<uint64_t>((size_t)S * cap);
+    lens = a.template take<int32_t>(S);
+    core_bytes = nms_core_workspace_size(S, cap);
+    core_ws = a.template take<char>(core_bytes);
+  }
+};
+
 }  // namespace
 
-size_t nms_sorted_workspace_size(int S, int cap) {
-  const int T = (cap + 63) / 64;
-  WorkspaceSizer z;
-  z.take<uint64_t>((size_t)S * cap * T);  // mask
-  z.take<uint64_t>((size_t)S * T * 2 * 64);  // column words (the fixed-point scan)
-  return z.off;
-}
+size_t nms_sorted_workspace_size(int S, int cap) { return layout_bytes<SortedSpace>(S, cap); }
 
 int nms_sorted(const float4* sboxes, const int32_t* sidx, const int32_t* count, int S, int cap,
                int max_out, float iou_thr, int32_t* keep, int32_t* num_keep, void* ws,
@@ -390,8 +410,9 @@ int nms_sorted(const float4* sboxes, const int32_t* sidx, const int32_t* count, 
   }
   const int T = (cap + 63) / 64;
   Workspace w(ws, ws_bytes);
-  uint64_t* mask = w.take<uint64_t>((size_t)S * cap * T);
-  uint64_t* colw = w.take<uint64_t>((size_t)S * T * 2 * 64);
+  SortedSpace o;
+  o.lay(w, S, cap);
+  uint64_t *mask = o.mask, *colw = o.colw;
   D2MI_REQUIRE(w.ok(), "NMS mask workspace too small (%zu < %zu)", ws_bytes, w.off);
   // tuning "nms_scan": 1 the fixed-point scan (r5) where its removal words
   // fit one propagation lane per tile (T <= 64: <= 4,096 candidates), 0 the
@@ -412,41 +433,26 @@ int nms_sorted(const float4* sboxes, const int32_t* sidx, const int32_t* count, 
   return 0;
 }
 
-size_t nms_core_workspace_size(int S, int cap) {
-  WorkspaceSizer z;
-  z.take<uint64_t>((size_t)S * cap);      // sorted keys
-  z.take<float4>((size_t)S * cap);        // sorted boxes
-  z.take<int32_t>((size_t)S * cap);       // sorted local idx
-  z.take<int32_t>(S);                     // count
-  z.take<char>(nms_sorted_workspace_size(S, cap));
-  z.take<char>(sort_workspace_size(S, cap));
-  return z.off;
-}
+size_t nms_core_workspace_size(int S, int cap) { return layout_bytes<NmsCoreSpace>(S, cap); }
 
 int nms_core(const uint64_t* keys, const int32_t* lens, const float4* boxes,
              const int32_t* box_off, int S, int cap, int max_out, float iou_thr, int32_t* keep,
              int32_t* num_keep, void* ws, size_t ws_bytes, hipStream_t stream) {
   if (S == 0) return 0;
   Workspace w(ws, ws_bytes);
-  uint64_t* sorted = w.take<uint64_t>((size_t)S * cap);
-  float4* sboxes = w.take<float4>((size_t)S * cap);
-  int32_t* idx = w.take<int32_t>((size_t)S * cap);
-  int32_t* count = w.take<int32_t>(S);
-  const size_t mask_bytes = nms_sorted_workspace_size(S, cap);
-  void* mask_ws = w.take<char>(mask_bytes);
-  const size_t sort_bytes = sort_workspace_size(S, cap);
-  void* sort_ws = w.take<char>(sort_bytes);
+  NmsCoreSpace o;
+  o.lay(w, S, cap);
   D2MI_REQUIRE(w.ok(), "NMS workspace too small (%zu < %zu)", ws_bytes, w.off);
   if (cap > 0) {
-    int rc = sort_keys_segmented(keys, sorted, lens, S, cap, sort_ws, sort_bytes, stream);
+    int rc = sort_keys_segmented(keys, o.sorted, lens, S, cap, o.sort_ws, o.sort_bytes, stream);
     if (rc) return rc;
     const int gx = std::min((cap + 255) / 256, 64);
-    hipLaunchKernelGGL(nms_prep_kernel, dim3(gx, S), dim3(256), 0, stream, sorted, lens, boxes,
-                       box_off, cap, sboxes, idx, count);
+    hipLaunchKernelGGL(nms_prep_kernel, dim3(gx, S), dim3(256), 0, stream, o.sorted, lens, boxes,
+                       box_off, cap, o.sboxes, o.idx, o.count);
     D2MI_LAUNCH_CHECK();
   }
-  return nms_sorted(sboxes, idx, count, S, cap, max_out, iou_thr, keep, num_keep, mask_ws,
-                    mask_bytes, stream);
+  return nms_sorted(o.sboxes, o.idx, o.count, S, cap, max_out, iou_thr, keep, num_keep, o.mask_ws,
+                    o.mask_bytes, stream);
 }
 
 }  // namespace d2mi
@@ -454,11 +460,7 @@ int nms_core(const uint64_t* keys, const int32_t* lens, const float4* boxes,
 using namespace d2mi;
 
 extern "C" size_t d2mi_nms_workspace_size(int num_segs, int seg_capacity) {
-  WorkspaceSizer z;
-  z.take<uint64_t>((size_t)num_segs * seg_capacity);
-  z.take<int32_t>(num_segs);
-  z.take<char>(nms_core_workspace_size(num_segs, seg_capacity));
-  return z.off;
+  return layout_bytes<NmsSpace>(num_segs, seg_capacity);
 }
 
 extern "C" int d2mi_nms(const float* boxes, const float* scores, const int32_t* seg_offsets,
@@ -473,17 +475,16 @@ extern "C" int d2mi_nms(const float* boxes, const float* scores, const int32_t* 
   if (num_segs == 0) return 0;
   hipStream_t st = as_stream(stream);
   Workspace w(workspace, workspace_bytes);
-  uint64_t* keys = w.take<uint64_t>((size_t)num_segs * seg_capacity);
-  int32_t* lens = w.take<int32_t>(num_segs);
-  const size_t core = nms_core_workspace_size(num_segs, seg_capacity);
-  void* core_ws = w.take<char>(core);
+  NmsSpace o;
+  o.lay(w, num_segs, seg_capacity);
   D2MI_REQUIRE(w.ok(), "NMS workspace too small (%zu < %zu)", workspace_bytes, w.off);
   int32_t* err = error_word();
   const int gx = std::max(1, std::min((seg_capacity + 255) / 256, 64));
   hipLaunchKernelGGL(nms_keys_kernel, dim3(gx, num_segs), dim3(256), 0, st, scores, seg_offsets,
-                     num_segs, seg_capacity, keys, lens, err);
+                     num_segs, seg_capacity, o.keys, o.lens, err);
   D2MI_LAUNCH_CHECK();
   // segment boxes start at seg_offsets[s]
-  return nms_core(keys, lens, reinterpret_cast<const float4*>(boxes), seg_offsets, num_segs,
-                  seg_capacity, max_out, iou_threshold, keep, num_keep, core_ws, core, st);
+  return nms_core(o.keys, o.lens, reinterpret_cast<const float4*>(boxes), seg_offsets, num_segs,
+                  seg_capacity, max_out, iou_threshold, keep, num_keep, o.core_ws, o.core_bytes,
+                  st);
 }

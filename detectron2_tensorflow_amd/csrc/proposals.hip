@@ -646,37 +646,23 @@ struct RpnWs {
   int32_t* num_keep;
   void* nms_ws;
   size_t nms_bytes;
-};
-
-template <typename WS>
-void rpn_layout(WS& w, RpnWs* o, int N, int L, int k, int post) {
-  const int S = N * L;
-  auto p0 = w.template take<int64_t>(S);
-  auto p1 = w.template take<int32_t>(S);
-  auto p2 = w.template take<float>((size_t)S * k);
-  auto p3 = w.template take<int32_t>((size_t)S * k);
-  auto p4 = w.template take<int32_t>(S);
-  const size_t tb = topk_workspace_size(S, k);
-  auto p5 = w.template take<char>(tb);
-  auto p6 = w.template take<float4>((size_t)S * k);
-  auto p7 = w.template take<uint64_t>((size_t)S * k);
-  auto p8 = w.template take<int32_t>(S);
-  auto p9 = w.template take<int32_t>((size_t)S * post);
-  auto p10 = w.template take<int32_t>(S);
-  const size_t nb = nms_core_workspace_size(S, k);
-  auto p11 = w.template take<char>(nb);
-  if (o) {
-    *o = RpnWs{(int64_t*)p0, (int32_t*)p1, (float*)p2, (int32_t*)p3, (int32_t*)p4, (void*)p5, tb,
-               (float4*)p6, (uint64_t*)p7, (int32_t*)p8, (int32_t*)p9, (int32_t*)p10, (void*)p11, nb};
-  }
-}
-
-struct SizerPtr {
-  WorkspaceSizer z;
-  template <typename T>
-  T* take(size_t n) {
-    z.take<T>(n);
-    return nullptr;
+  template <typename A>
+  void lay(A& a, int N, int L, int k, int post) {
+    const int S = N * L;
+    seg_start = a.template take<int64_t>(S);
+    seg_len = a.template take<int32_t>(S);
+    tvals = a.template take<float>((size_t)S * k);
+    tidx = a.template take<int32_t>((size_t)S * k);
+    tcount = a.template take<int32_t>(S);
+    topk_bytes = topk_workspace_size(S, k);
+    topk_ws = a.template take<char>(topk_bytes);
+    dec = a.template take<float4>((size_t)S * k);
+    keys = a.template take<uint64_t>((size_t)S * k);
+    lens = a.template take<int32_t>(S);
+    keep = a.template take<int32_t>((size_t)S * post);
+    num_keep = a.template take<int32_t>(S);
+    nms_bytes = nms_core_workspace_size(S, k);
+    nms_ws = a.template take<char>(nms_bytes);
   }
 };
 }  // namespace
@@ -686,9 +672,7 @@ extern "C" size_t d2mi_rpn_proposals_workspace_size(int N, int L, const int32_t*
   int maxlen = 0;
   for (int l = 0; l < L; ++l) maxlen = std::max(maxlen, level_hw[2 * l] * level_hw[2 * l + 1] * A);
   const int k = std::max(1, std::min(pre_nms_topk, maxlen));
-  SizerPtr s;
-  rpn_layout(s, nullptr, N, L, k, post_nms_topk);
-  return s.z.off;
+  return layout_bytes<RpnWs>(N, L, k, post_nms_topk);
 }
 
 extern "C" int d2mi_rpn_proposals(const float* const* logits, const float* const* deltas,
@@ -741,7 +725,7 @@ extern "C" int d2mi_rpn_proposals_ex(const float* const* logits, const float* co
   const int S = N * L;
   Workspace w(workspace, workspace_bytes);
   RpnWs o;
-  rpn_layout(w, &o, N, L, k, post_nms_topk);
+  o.lay(w, N, L, k, post_nms_topk);
   D2MI_REQUIRE(w.ok(), "RPN workspace too small (%zu < %zu)", workspace_bytes, w.off);
   hipLaunchKernelGGL(seg_setup_kernel, dim3((S + 63) / 64), dim3(64), 0, st, lv, N, 1, k,
                      o.seg_start, o.seg_len, (int32_t*)nullptr);
@@ -750,21 +734,17 @@ extern "C" int d2mi_rpn_proposals_ex(const float* const* logits, const float* co
                     o.tcount, o.topk_ws, o.topk_bytes, st);
   if (rc) return rc;
   if (tuning(kTuneRpnCompact) != 0) {
-    // the NMS workspace carved as nms_core carves it (its sort keys unused)
+    // nms_core's own layout of the NMS workspace (its sort keys unused)
     Workspace nw(o.nms_ws, o.nms_bytes);
-    nw.take<uint64_t>((size_t)S * k);
-    float4* sboxes = nw.take<float4>((size_t)S * k);
-    int32_t* sidx = nw.take<int32_t>((size_t)S * k);
-    int32_t* scount = nw.take<int32_t>(S);
-    const size_t mask_bytes = nms_sorted_workspace_size(S, k);
-    void* mask_ws = nw.take<char>(mask_bytes);
+    NmsCoreSpace c;
+    c.lay(nw, S, k);
     D2MI_REQUIRE(nw.ok(), "RPN NMS workspace too small");
     hipLaunchKernelGGL(rpn_decode_compact_kernel, dim3(S), dim3(1024), 0, st, deltas[0], lv, N, k,
                        o.tvals, o.tidx, o.tcount, image_hw, make_dc(weights4_host, scale_clamp),
-                       min_box_side_len, o.dec, sboxes, sidx, scount);
+                       min_box_side_len, o.dec, c.sboxes, c.idx, c.count);
     D2MI_LAUNCH_CHECK();
-    rc = nms_sorted(sboxes, sidx, scount, S, k, post_nms_topk, nms_thresh, o.keep, o.num_keep,
-                    mask_ws, mask_bytes, st);
+    rc = nms_sorted(c.sboxes, c.idx, c.count, S, k, post_nms_topk, nms_thresh, o.keep, o.num_keep,
+                    c.mask_ws, c.mask_bytes, st);
     if (rc) return rc;
   } else {  // decode -> keys -> nms_core's sort + gather (A/B)
     hipLaunchKernelGGL(rpn_decode_kernel, dim3(grid1(k, 256, 64), S), dim3(256), 0, st, deltas[0],
@@ -814,39 +794,33 @@ struct FrcnnWs {
   size_t sort_bytes;
   void* nms_ws;
   size_t nms_bytes;
+  template <typename A>
+  void lay(A& a, int N, int P, int K, int cap, int max_det) {
+    slot2roi = a.template take<int32_t>((size_t)N * P);
+    maxc = a.template take<uint32_t>(N);
+    cnt = a.template take<int32_t>(N);
+    keys = a.template take<uint64_t>((size_t)N * cap);
+    cbox = a.template take<float4>((size_t)N * cap);
+    cscore = a.template take<float>((size_t)N * cap);
+    flat2pos = a.template take<int32_t>((size_t)N * P * K);
+    sorted = a.template take<uint64_t>((size_t)N * cap);
+    sboxes = a.template take<float4>((size_t)N * cap);
+    sidx = a.template take<int32_t>((size_t)N * cap);
+    count = a.template take<int32_t>(N);
+    keep = a.template take<int32_t>((size_t)N * max_det);
+    num_keep = a.template take<int32_t>(N);
+    sort_bytes = sort_workspace_size(N, cap);
+    sort_ws = a.template take<char>(sort_bytes);
+    nms_bytes = nms_sorted_workspace_size(N, cap);
+    nms_ws = a.template take<char>(nms_bytes);
+  }
 };
-template <typename WS>
-void frcnn_layout(WS& w, FrcnnWs* o, int N, int P, int K, int cap, int max_det) {
-  auto a0 = w.template take<int32_t>((size_t)N * P);
-  auto a1 = w.template take<uint32_t>(N);
-  auto a2 = w.template take<int32_t>(N);
-  auto a3 = w.template take<uint64_t>((size_t)N * cap);
-  auto a4 = w.template take<float4>((size_t)N * cap);
-  auto a5 = w.template take<float>((size_t)N * cap);
-  auto a6 = w.template take<int32_t>((size_t)N * P * K);
-  auto a7 = w.template take<uint64_t>((size_t)N * cap);
-  auto a8 = w.template take<float4>((size_t)N * cap);
-  auto a9 = w.template take<int32_t>((size_t)N * cap);
-  auto a10 = w.template take<int32_t>(N);
-  auto a11 = w.template take<int32_t>((size_t)N * max_det);
-  auto a12 = w.template take<int32_t>(N);
-  const size_t sb = sort_workspace_size(N, cap);
-  auto a13 = w.template take<char>(sb);
-  const size_t nb = nms_sorted_workspace_size(N, cap);
-  auto a14 = w.template take<char>(nb);
-  if (o)
-    *o = FrcnnWs{(int32_t*)a0, (uint32_t*)a1, (int32_t*)a2, (uint64_t*)a3, (float4*)a4, (float*)a5,
-                 (int32_t*)a6, (uint64_t*)a7, (float4*)a8, (int32_t*)a9, (int32_t*)a10,
-                 (int32_t*)a11, (int32_t*)a12, (void*)a13, sb, (void*)a14, nb};
-}
 }  // namespace
 
 extern "C" size_t d2mi_fast_rcnn_workspace_size(int N, int P, int K, float score_thresh,
                                                 int max_det) {
-  SizerPtr s;
-  frcnn_layout(s, nullptr, N, std::max(1, P), K, frcnn_cap(std::max(1, P), K, score_thresh),
-               max_det);
-  return s.z.off;
+  return layout_bytes<FrcnnWs>(N, std::max(1, P), K, frcnn_cap(std::max(1, P), K, score_thresh),
+                               max_det);
 }
 
 extern "C" int d2mi_fast_rcnn_inference(const float* logits, const float* deltas,
@@ -870,7 +844,7 @@ extern "C" int d2mi_fast_rcnn_inference(const float* logits, const float* deltas
   const int cap = frcnn_cap(P, K, score_thresh);
   Workspace w(workspace, workspace_bytes);
   FrcnnWs o;
-  frcnn_layout(w, &o, N, P, K, cap, max_det);
+  o.lay(w, N, P, K, cap, max_det);
   D2MI_REQUIRE(w.ok(), "fast_rcnn workspace too small (%zu < %zu)", workspace_bytes, w.off);
   int32_t* err = error_word();
   D2MI_REQUIRE(fill_bytes(o.slot2roi, (size_t)N * P * 4, 0xff, st) == 0, "fill failed");
@@ -938,48 +912,40 @@ struct RetinaWs {
   size_t sort_bytes;
   void* nms_ws;
   size_t nms_bytes;
+  template <typename A>
+  void lay(A& a, int N, int L, int k, int max_det) {
+    const int S = N * L, cap = L * k;
+    seg_start = a.template take<int64_t>(S);
+    seg_len = a.template take<int32_t>(S);
+    seg_k = a.template take<int32_t>(S);
+    tvals = a.template take<float>((size_t)S * k);
+    tidx = a.template take<int32_t>((size_t)S * k);
+    tcount = a.template take<int32_t>(S);
+    topk_bytes = topk_workspace_size(S, k);
+    topk_ws = a.template take<char>(topk_bytes);
+    keys = a.template take<uint64_t>((size_t)N * cap);
+    cbox = a.template take<float4>((size_t)N * cap);
+    cscore = a.template take<float>((size_t)N * cap);
+    ccls = a.template take<int32_t>((size_t)N * cap);
+    maxc = a.template take<uint32_t>(N);
+    lens = a.template take<int32_t>(N);
+    sorted = a.template take<uint64_t>((size_t)N * cap);
+    sboxes = a.template take<float4>((size_t)N * cap);
+    sidx = a.template take<int32_t>((size_t)N * cap);
+    count = a.template take<int32_t>(N);
+    keep = a.template take<int32_t>((size_t)N * max_det);
+    num_keep = a.template take<int32_t>(N);
+    sort_bytes = sort_workspace_size(N, cap);
+    sort_ws = a.template take<char>(sort_bytes);
+    nms_bytes = nms_sorted_workspace_size(N, cap);
+    nms_ws = a.template take<char>(nms_bytes);
+  }
 };
-template <typename WS>
-void retina_layout(WS& w, RetinaWs* o, int N, int L, int k, int max_det) {
-  const int S = N * L, cap = L * k;
-  auto a0 = w.template take<int64_t>(S);
-  auto a1 = w.template take<int32_t>(S);
-  auto a2 = w.template take<int32_t>(S);
-  auto a3 = w.template take<float>((size_t)S * k);
-  auto a4 = w.template take<int32_t>((size_t)S * k);
-  auto a5 = w.template take<int32_t>(S);
-  const size_t tb = topk_workspace_size(S, k);
-  auto a6 = w.template take<char>(tb);
-  auto a7 = w.template take<uint64_t>((size_t)N * cap);
-  auto a8 = w.template take<float4>((size_t)N * cap);
-  auto a9 = w.template take<float>((size_t)N * cap);
-  auto a10 = w.template take<int32_t>((size_t)N * cap);
-  auto a11 = w.template take<uint32_t>(N);
-  auto a12 = w.template take<int32_t>(N);
-  auto a13 = w.template take<uint64_t>((size_t)N * cap);
-  auto a14 = w.template take<float4>((size_t)N * cap);
-  auto a15 = w.template take<int32_t>((size_t)N * cap);
-  auto a16 = w.template take<int32_t>(N);
-  auto a17 = w.template take<int32_t>((size_t)N * max_det);
-  auto a18 = w.template take<int32_t>(N);
-  const size_t sb = sort_workspace_size(N, cap);
-  auto a19 = w.template take<char>(sb);
-  const size_t nb = nms_sorted_workspace_size(N, cap);
-  auto a20 = w.template take<char>(nb);
-  if (o)
-    *o = RetinaWs{(int64_t*)a0, (int32_t*)a1, (int32_t*)a2, (float*)a3, (int32_t*)a4,
-                  (int32_t*)a5, (void*)a6, tb, (uint64_t*)a7, (float4*)a8, (float*)a9,
-                  (int32_t*)a10, (uint32_t*)a11, (int32_t*)a12, (uint64_t*)a13, (float4*)a14,
-                  (int32_t*)a15, (int32_t*)a16, (int32_t*)a17, (int32_t*)a18, (void*)a19, sb,
-                  (void*)a20, nb};
-}
 }  // namespace
 
 extern "C" size_t d2mi_retinanet_workspace_size(int N, int L, const int32_t* level_hw, int A,
                                                 int K, int topk_candidates) {
-  SizerPtr s;
-  retina_layout(s, nullptr, N, L, std::max(1, topk_candidates), 1000);
-  size_t z = s.z.off;
+  size_t z = layout_bytes<RetinaWs>(N, L, std::max(1, topk_candidates), 1000);
   if (retina_fused_eligible(L, topk_candidates, 1000))
     z = std::max(z, retina_fused_workspace_size(N, L, level_hw, A, K, topk_candidates));
   return z;
@@ -1012,7 +978,7 @@ extern "C" int d2mi_retinanet_inference(const float* const* cls, const float* co
   const int S = N * L, cap = L * k;
   Workspace w(workspace, workspace_bytes);
   RetinaWs o;
-  retina_layout(w, &o, N, L, k, max_det);
+  o.lay(w, N, L, k, max_det);
   D2MI_REQUIRE(w.ok(), "retinanet workspace too small (%zu < %zu)", workspace_bytes, w.off);
   hipLaunchKernelGGL(seg_setup_kernel, dim3((S + 63) / 64), dim3(64), 0, st, lv, N, K, k,
                      o.seg_start, o.seg_len, o.seg_k);

@@ -1471,34 +1471,22 @@ struct FusedWs {
   uint16_t* ord;
   uint64_t* cand;
   int32_t* pcnt;
-};
-template <typename WS>
-void fused_layout(WS& w, FusedWs* o, int N, int L, int k, int chunks, int parts) {
-  const int S = N * L;
-  const size_t C = (size_t)N * L * k;
-  auto a0 = w.template take<SegInfo>(S);
-  auto a1 = w.template take<int32_t>((size_t)chunks * kCW);
-  auto a2 = w.template take<uint64_t>((size_t)chunks * kCW * kWaveSlots);
-  auto a3 = w.template take<uint64_t>((size_t)S * kCap);
-  auto a4 = w.template take<float>(C);
-  auto a5 = w.template take<float4>(C);
-  auto a6 = w.template take<int32_t>(C);
-  auto a7 = w.template take<int32_t>(S);
-  auto a8 = w.template take<uint32_t>(N);
-  auto a9 = w.template take<uint16_t>(C);
-  auto a10 = w.template take<uint64_t>((size_t)parts * kPartCap);
-  auto a11 = w.template take<int32_t>((size_t)parts);
-  if (o)
-    *o = FusedWs{(SegInfo*)a0, (int32_t*)a1, (uint64_t*)a2, (uint64_t*)a3, (float*)a4,
-                 (float4*)a5, (int32_t*)a6, (int32_t*)a7, (uint32_t*)a8, (uint16_t*)a9,
-                 (uint64_t*)a10, (int32_t*)a11};
-}
-struct SizerP {
-  WorkspaceSizer z;
-  template <typename T>
-  T* take(size_t n) {
-    z.take<T>(n);
-    return nullptr;
+  template <typename A>
+  void lay(A& a, int N, int L, int k, int chunks, int parts) {
+    const int S = N * L;
+    const size_t C = (size_t)N * L * k;
+    info = a.template take<SegInfo>(S);
+    wcount = a.template take<int32_t>((size_t)chunks * kCW);
+    wslot = a.template take<uint64_t>((size_t)chunks * kCW * kWaveSlots);
+    ovf = a.template take<uint64_t>((size_t)S * kCap);
+    cscore = a.template take<float>(C);
+    cbox = a.template take<float4>(C);
+    ccls = a.template take<int32_t>(C);
+    lvl_cnt = a.template take<int32_t>(S);
+    maxc = a.template take<uint32_t>(N);
+    ord = a.template take<uint16_t>(C);
+    cand = a.template take<uint64_t>((size_t)parts * kPartCap);
+    pcnt = a.template take<int32_t>((size_t)parts);
   }
 };
 
@@ -1533,9 +1521,7 @@ bool retina_fused_eligible(int L, int k, int max_det) {
 size_t retina_fused_workspace_size(int N, int L, const int32_t* level_hw, int A, int K, int k) {
   RetinaGeo g;
   if (!make_geo(g, level_hw, L, A, K, N)) return 0;
-  SizerP s;
-  fused_layout(s, nullptr, N, L, k, N * g.chunk0[L], N * g.part0[L]);
-  return s.z.off;
+  return layout_bytes<FusedWs>(N, L, k, N * g.chunk0[L], N * g.part0[L]);
 }
 
 int retinanet_fused(const float* const* cls, const float* const* box, const Levels& lv,
@@ -1564,7 +1550,7 @@ int retinanet_fused(const float* const* cls, const float* const* box, const Leve
   const int chunks = N * g.chunk0[L];
   Workspace w(workspace, workspace_bytes);
   FusedWs o;
-  fused_layout(w, &o, N, L, k, chunks, N * g.part0[L]);
+  o.lay(w, N, L, k, chunks, N * g.part0[L]);
   D2MI_REQUIRE(w.ok(), "retinanet workspace too small (%zu < %zu)", workspace_bytes, w.off);
   const int reps = (var & 4) ? 2 : 1;
   for (int rep = 0; rep < reps; ++rep) {

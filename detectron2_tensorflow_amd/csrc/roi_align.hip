@@ -1413,23 +1413,36 @@ int bwd_plan(const int32_t* dims, int num_levels, int R, int out_h, int out_w, i
   return bwd_plan_n(dims, num_levels, (long long)R * out_h * out_w * S * S, 0, p);
 }
 
-template <class WS>
-void bwd_layout(WS& w, int C, const BwdPlan& p) {
-  w.template take<uint64_t>((size_t)p.n_keys + 1);          // ent: pair << 32 | arrival rank
-  w.template take<int32_t>((size_t)p.n_keys + 1);           // arrival-ordered slots
-  w.template take<RunRec>((size_t)p.n_keys + 1);            // arrival-ordered run records
-  w.template take<int32_t>((size_t)p.n_keys + 1);           // long runs in slot order
-  w.template take<Contrib>((size_t)p.n_samples + 1);        // records
-  w.template take<int32_t>((size_t)p.pairs + 1);            // count
-  w.template take<int32_t>((size_t)p.pairs + 1);            // run_start
-  w.template take<int32_t>((size_t)p.pairs + 1);            // seg_first
-  w.template take<int32_t>((size_t)p.max_segs);             // seg_pixel
-  w.template take<float>((size_t)p.max_segs * C);           // partial rows
-  w.template take<int32_t>((size_t)p.max_touched + 1);      // touched pixels
-  w.template take<int4>(((size_t)p.max_touched + 1) * 2);   // their runs per set
-  w.template take<int2>((size_t)p.max_tasks);               // long-sort tasks
-  w.template take<BwdCounters>(1);
-}
+struct BwdSpace {
+  uint64_t* ent;         // pair << 32 | arrival rank
+  int32_t* arrival;      // arrival-ordered slots
+  RunRec* runrec;        // arrival-ordered run records
+  int32_t* sorted_long;  // long runs in slot order
+  Contrib* rec;          // records
+  int32_t *count, *run_start, *seg_first, *seg_pixel;
+  float* partial;    // partial rows
+  int32_t* touched;  // touched pixels
+  int4* trun;        // their runs per set
+  int2* tasks;       // long-sort tasks
+  BwdCounters* ctr;
+  template <typename A>
+  void lay(A& w, int C, const BwdPlan& p) {
+    ent = w.template take<uint64_t>((size_t)p.n_keys + 1);
+    arrival = w.template take<int32_t>((size_t)p.n_keys + 1);
+    runrec = w.template take<RunRec>((size_t)p.n_keys + 1);
+    sorted_long = w.template take<int32_t>((size_t)p.n_keys + 1);
+    rec = w.template take<Contrib>((size_t)p.n_samples + 1);
+    count = w.template take<int32_t>((size_t)p.pairs + 1);
+    run_start = w.template take<int32_t>((size_t)p.pairs + 1);
+    seg_first = w.template take<int32_t>((size_t)p.pairs + 1);
+    seg_pixel = w.template take<int32_t>((size_t)p.max_segs);
+    partial = w.template take<float>((size_t)p.max_segs * C);
+    touched = w.template take<int32_t>((size_t)p.max_touched + 1);
+    trun = w.template take<int4>(((size_t)p.max_touched + 1) * 2);
+    tasks = w.template take<int2>((size_t)p.max_tasks);
+    ctr = w.template take<BwdCounters>(1);
+  }
+};
 
 // The backward over nsets (1 or 2) ROI sets of the same maps; sets[k] holds
 // each set's ROIs / crop / grad_out (everything else equal).
@@ -1460,26 +1473,12 @@ int roi_bwd_core(const RoiArgs* sets, int nsets, const int32_t* dims, int num_le
   BwdPlan p;
   int rc = bwd_plan_n(dims, num_levels, ns[0] + ns[1], sb, &p);
   if (rc) return rc;
-  WorkspaceSizer z;
-  bwd_layout(z, C, p);
-  D2MI_REQUIRE(workspace_bytes >= z.off && (workspace || z.off == 0),
-               "ROIAlign backward workspace too small: %zu < %zu", workspace_bytes, z.off);
-  if (p.total_pixels == 0) return 0;
   Workspace w(workspace, workspace_bytes);
-  uint64_t* ent = w.take<uint64_t>((size_t)p.n_keys + 1);
-  int32_t* arrival = w.take<int32_t>((size_t)p.n_keys + 1);
-  RunRec* runrec = w.take<RunRec>((size_t)p.n_keys + 1);
-  int32_t* sorted_long = w.take<int32_t>((size_t)p.n_keys + 1);
-  Contrib* rec = w.take<Contrib>((size_t)p.n_samples + 1);
-  int32_t* count = w.take<int32_t>((size_t)p.pairs + 1);
-  int32_t* run_start = w.take<int32_t>((size_t)p.pairs + 1);
-  int32_t* seg_first = w.take<int32_t>((size_t)p.pairs + 1);
-  int32_t* seg_pixel = w.take<int32_t>((size_t)p.max_segs);
-  float* partial = w.take<float>((size_t)p.max_segs * C);
-  int32_t* touched = w.take<int32_t>((size_t)p.max_touched + 1);
-  int4* trun = w.take<int4>(((size_t)p.max_touched + 1) * 2);
-  int2* tasks = w.take<int2>((size_t)p.max_tasks);
-  BwdCounters* ctr = w.take<BwdCounters>(1);
+  BwdSpace s;
+  s.lay(w, C, p);
+  D2MI_REQUIRE(w.ok() && (workspace || w.off == 0),
+               "ROIAlign backward workspace too small: %zu < %zu", workspace_bytes, w.off);
+  if (p.total_pixels == 0) return 0;
   // r5: the C = 256 pixel pass reads run records (tuning "roi_bwd_rec", 1);
   // 0 = the r4 slot pass (A/B).  Phase 1 and phase 2 of one backward must
   // see the same value (a deferred pass reads what the prepare wrote).
@@ -1497,8 +1496,8 @@ int roi_bwd_core(const RoiArgs* sets, int nsets, const int32_t* dims, int num_le
   for (int l = lv_lo; l <= lv_hi; ++l)  // untouched pixels: zero (accumulated levels: kept)
     if (!((acc_mask >> l) & 1))
       clear(a.gfeat[l], (long long)dims[3 * l] * dims[3 * l + 1] * dims[3 * l + 2] * C, 0u);
-  clear(count, p.pairs, 0u);
-  clear(ctr, sizeof(BwdCounters) / 4, 0u);
+  clear(s.count, p.pairs, 0u);
+  clear(s.ctr, sizeof(BwdCounters) / 4, 0u);
   hipLaunchKernelGGL(roi_bwd_clear_kernel,
                      dim3((unsigned)std::max(1LL, std::min((clear_words / 4 + 255) / 256, 8192LL))),
                      dim3(256), 0, st, cl);
@@ -1508,17 +1507,19 @@ int roi_bwd_core(const RoiArgs* sets, int nsets, const int32_t* dims, int num_le
     const int nb0 = (int)((ns[0] + 255) / 256), nb1 = nsets > 1 ? (int)((ns[1] + 255) / 256) : 0;
     if (nb0 + nb1 > 0) {
       hipLaunchKernelGGL(roi_bwd_emit_kernel, dim3((unsigned)(nb0 + nb1)), dim3(256), 0, st,
-                         sets[0], sets[nsets > 1 ? 1 : 0], nb0, ns[0], p.pm, sb, count, ent, rec);
+                         sets[0], sets[nsets > 1 ? 1 : 0], nb0, ns[0], p.pm, sb, s.count, s.ent,
+                         s.rec);
       D2MI_LAUNCH_CHECK();
     }
   }
   hipLaunchKernelGGL(roi_bwd_runs_kernel, dim3((unsigned)((p.total_pixels + 1023) / 1024)),
-                     dim3(1024), 0, st, count, p.total_pixels, sb, run_start, seg_first, seg_pixel,
-                     tasks, touched, use_runrec ? trun : nullptr, ctr, p.pm,
+                     dim3(1024), 0, st, s.count, p.total_pixels, sb, s.run_start, s.seg_first,
+                     s.seg_pixel, s.tasks, s.touched, use_runrec ? s.trun : nullptr, s.ctr, p.pm,
                      tuning(kTuneRoiHeavy));
   D2MI_LAUNCH_CHECK();
   hipLaunchKernelGGL(roi_bwd_place_kernel, dim3((unsigned)((p.n_keys + 255) / 256)), dim3(256), 0,
-                     st, ent, p.n_keys, run_start, arrival, rec, use_runrec ? runrec : nullptr);
+                     st, s.ent, p.n_keys, s.run_start, s.arrival, s.rec,
+                     use_runrec ? s.runrec : nullptr);
   D2MI_LAUNCH_CHECK();
   // long runs (degenerate piles of boxes) in slot order, then their segment
   // partials: grid-stride loops over the device-side task / segment counts
@@ -1527,8 +1528,8 @@ int roi_bwd_core(const RoiArgs* sets, int nsets, const int32_t* dims, int num_le
   // and exits is most of these launches' cost in an ordinary step)
   hipLaunchKernelGGL((vec4 ? roi_bwd_long_kernel<true> : roi_bwd_long_kernel<false>),
                      dim3((unsigned)std::max(1LL, std::min<long long>(p.max_tasks, 64LL))),
-                     dim3(1024), 0, st, a, arrival, count, run_start, tasks, ctr, sorted_long, rec,
-                     seg_first, seg_pixel, partial);
+                     dim3(1024), 0, st, a, s.arrival, s.count, s.run_start, s.tasks, s.ctr,
+                     s.sorted_long, s.rec, s.seg_first, s.seg_pixel, s.partial);
   D2MI_LAUNCH_CHECK();
   }  // phase 1
   if (phase == 2) {  // a pixel pass alone: its non-accumulated maps start from zero
@@ -1570,29 +1571,31 @@ int roi_bwd_core(const RoiArgs* sets, int nsets, const int32_t* dims, int num_le
     const dim3 g4((unsigned)std::max(1LL, std::min((cap + 4 * pw - 1) / (4 * pw), wg_max)));
     if (!use_runrec)  // the r4 pixel pass (A/B)
       hipLaunchKernelGGL(roi_bwd_pixel_c256_slots_kernel<4>, g4, dim3(256), 0, st, a, p.pm,
-                         arrival, rec, sb, count, run_start, seg_first, partial, touched, ctr,
-                         lv_lo, lv_hi);
+                         s.arrival, s.rec, sb, s.count, s.run_start, s.seg_first, s.partial,
+                         s.touched, s.ctr, lv_lo, lv_hi);
     else if (ppw == 8)
-      hipLaunchKernelGGL((roi_bwd_pixel_c256_kernel<8, 4>), g4, dim3(256), 0, st, a, p.pm, runrec,
-                         sb, trun, partial, ctr, lv_lo, lv_hi);
+      hipLaunchKernelGGL((roi_bwd_pixel_c256_kernel<8, 4>), g4, dim3(256), 0, st, a, p.pm, s.runrec,
+                         sb, s.trun, s.partial, s.ctr, lv_lo, lv_hi);
     else if (tv == 2)
-      hipLaunchKernelGGL((roi_bwd_pixel_c256_kernel<4, 2>), g4, dim3(256), 0, st, a, p.pm, runrec,
-                         sb, trun, partial, ctr, lv_lo, lv_hi);
+      hipLaunchKernelGGL((roi_bwd_pixel_c256_kernel<4, 2>), g4, dim3(256), 0, st, a, p.pm, s.runrec,
+                         sb, s.trun, s.partial, s.ctr, lv_lo, lv_hi);
     else if (tv == 3)
-      hipLaunchKernelGGL((roi_bwd_pixel_c256_kernel<4, 4>), g4, dim3(256), 0, st, a, p.pm, runrec,
-                         sb, trun, partial, ctr, lv_lo, lv_hi);
+      hipLaunchKernelGGL((roi_bwd_pixel_c256_kernel<4, 4>), g4, dim3(256), 0, st, a, p.pm, s.runrec,
+                         sb, s.trun, s.partial, s.ctr, lv_lo, lv_hi);
     else if (tv == 5)
-      hipLaunchKernelGGL((roi_bwd_pixel_c256_kernel<1, 8>), g4, dim3(256), 0, st, a, p.pm, runrec,
-                         sb, trun, partial, ctr, lv_lo, lv_hi);
+      hipLaunchKernelGGL((roi_bwd_pixel_c256_kernel<1, 8>), g4, dim3(256), 0, st, a, p.pm, s.runrec,
+                         sb, s.trun, s.partial, s.ctr, lv_lo, lv_hi);
     else
-      hipLaunchKernelGGL((roi_bwd_pixel_c256_kernel<2, 4>), g4, dim3(256), 0, st, a, p.pm, runrec,
-                         sb, trun, partial, ctr, lv_lo, lv_hi);
+      hipLaunchKernelGGL((roi_bwd_pixel_c256_kernel<2, 4>), g4, dim3(256), 0, st, a, p.pm, s.runrec,
+                         sb, s.trun, s.partial, s.ctr, lv_lo, lv_hi);
   } else if (vec4) {
-    hipLaunchKernelGGL(roi_bwd_pixel_kernel<true>, grid, dim3(256), 0, st, a, p.pm, arrival, rec,
-                       sb, count, run_start, seg_first, partial, touched, ctr, lv_lo, lv_hi);
+    hipLaunchKernelGGL(roi_bwd_pixel_kernel<true>, grid, dim3(256), 0, st, a, p.pm, s.arrival,
+                       s.rec, sb, s.count, s.run_start, s.seg_first, s.partial, s.touched, s.ctr,
+                       lv_lo, lv_hi);
   } else {
-    hipLaunchKernelGGL(roi_bwd_pixel_kernel<false>, grid, dim3(256), 0, st, a, p.pm, arrival, rec,
-                       sb, count, run_start, seg_first, partial, touched, ctr, lv_lo, lv_hi);
+    hipLaunchKernelGGL(roi_bwd_pixel_kernel<false>, grid, dim3(256), 0, st, a, p.pm, s.arrival,
+                       s.rec, sb, s.count, s.run_start, s.seg_first, s.partial, s.touched, s.ctr,
+                       lv_lo, lv_hi);
   }
   D2MI_LAUNCH_CHECK();
   return 0;
@@ -1607,9 +1610,7 @@ extern "C" size_t d2mi_roi_align_bwd_workspace_size(const int32_t* dims, int num
   if (!dims || num_levels < 1 || num_levels > D2MI_MAX_LEVELS || R < 0 || C < 1) return 0;
   BwdPlan p;
   if (bwd_plan(dims, num_levels, R, out_h, out_w, sampling_ratio, &p)) return 0;
-  WorkspaceSizer w;
-  bwd_layout(w, C, p);
-  return w.off;
+  return layout_bytes<BwdSpace>(C, p);
 }
 
 extern "C" int d2mi_roi_align_bwd_ex(float* const* grad_feats, const int32_t* dims,
@@ -1646,9 +1647,7 @@ extern "C" size_t d2mi_roi_align_bwd2_workspace_size(const int32_t* dims, int nu
                  (long long)R0 * out_h0 * out_w0 * S0 * S0 + (long long)R1 * out_h1 * out_w1 * S1 * S1,
                  1, &p))
     return 0;
-  WorkspaceSizer w;
-  bwd_layout(w, C, p);
-  return w.off;
+  return layout_bytes<BwdSpace>(C, p);
 }
 
 extern "C" int d2mi_roi_align_bwd2_ex(float* const* grad_feats, const int32_t* dims,

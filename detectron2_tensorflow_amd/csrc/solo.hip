@@ -1074,15 +1074,29 @@ extern "C" int d2mi_solo_mask_stats(const float* logits, int R, int P, float mas
   return 0;
 }
 
+namespace {
+struct SelectSpace {
+  float* dense;
+  int32_t* valid;
+  int64_t* seg_start;
+  int32_t *seg_len, *top_idx;
+  void* tk_ws;
+  size_t tk_bytes;
+  template <typename A>
+  void lay(A& a, int N, int T, int K, int k) {
+    dense = a.template take<float>((size_t)N * T * K);
+    valid = a.template take<int32_t>(N);
+    seg_start = a.template take<int64_t>(N);
+    seg_len = a.template take<int32_t>(N);
+    top_idx = a.template take<int32_t>((size_t)N * k);
+    tk_bytes = topk_workspace_size(N, k);
+    tk_ws = a.template take<char>(tk_bytes);
+  }
+};
+}  // namespace
+
 extern "C" size_t d2mi_solo_select_workspace_size(int N, int T, int K, int k) {
-  WorkspaceSizer z;
-  z.take<float>((size_t)N * T * K);
-  z.take<int32_t>(N);
-  z.take<int64_t>(N);
-  z.take<int32_t>(N);
-  z.take<int32_t>((size_t)N * k);
-  z.off += topk_workspace_size(N, k) + 256;
-  return z.off;
+  return layout_bytes<SelectSpace>(N, T, K, k);
 }
 
 extern "C" int d2mi_solo_select(const float* probs, const int32_t* live_row,
@@ -1102,24 +1116,19 @@ extern "C" int d2mi_solo_select(const float* probs, const int32_t* live_row,
   const int W64 = (P + 63) / 64;
   hipStream_t st = as_stream(stream);
   Workspace w(workspace, workspace_bytes);
-  float* dense = w.take<float>((size_t)N * T * K);
-  int32_t* valid = w.take<int32_t>(N);
-  int64_t* seg_start = w.take<int64_t>(N);
-  int32_t* seg_len = w.take<int32_t>(N);
-  int32_t* top_idx = w.take<int32_t>((size_t)N * k);
-  const size_t tk_bytes = topk_workspace_size(N, k);
-  void* tk_ws = w.take<char>(tk_bytes);
+  SelectSpace o;
+  o.lay(w, N, T, K, k);
   D2MI_REQUIRE(w.ok(), "SOLO select workspace too small (%zu < %zu)", workspace_bytes, w.off);
-  D2MI_REQUIRE(fill_bytes(valid, sizeof(int32_t) * N, 0, st) == 0, "fill failed");
+  D2MI_REQUIRE(fill_bytes(o.valid, sizeof(int32_t) * N, 0, st) == 0, "fill failed");
   const size_t total = (size_t)N * T * K;
   hipLaunchKernelGGL(solo_cand_kernel, dim3(grid_for(std::max(total, (size_t)N), 256)),
                      dim3(256), 0, st, lv, probs, live_row, row_off, sum_masks, sum_scores, N, K,
-                     score_thr, dense, valid, seg_start, seg_len);
+                     score_thr, o.dense, o.valid, o.seg_start, o.seg_len);
   D2MI_LAUNCH_CHECK();
-  int rc = topk_core_ex(dense, seg_start, seg_len, valid, N, T * K, k, 0, top_scores, top_idx,
-                        top_count, tk_ws, tk_bytes, st);
+  int rc = topk_core_ex(o.dense, o.seg_start, o.seg_len, o.valid, N, T * K, k, 0, top_scores,
+                        o.top_idx, top_count, o.tk_ws, o.tk_bytes, st);
   if (rc) return rc;
-  hipLaunchKernelGGL(solo_gather_kernel, dim3(k, N), dim3(256), 0, st, top_idx, top_count,
+  hipLaunchKernelGGL(solo_gather_kernel, dim3(k, N), dim3(256), 0, st, o.top_idx, top_count,
                      live_row, row_off, logits, sum_masks, T, K, P, k, W64, mask_thr, top_classes,
                      top_sum_masks, mask_bits);
   D2MI_LAUNCH_CHECK();
@@ -1136,15 +1145,25 @@ static int solo_mfma_groups(int N, int k, int W64) {
   return std::min(want, most);
 }
 
+namespace {
+struct SoloNmsSpace {
+  int32_t* inter;
+  float* comp;
+  int32_t* part;  // the MFMA path's partial tiles (groups > 0)
+  template <typename A>
+  void lay(A& a, int N, int k, int groups) {
+    inter = a.template take<int32_t>((size_t)N * k * k);
+    comp = a.template take<float>((size_t)N * k);
+    const int T = (k + kIT - 1) / kIT, tri = T * (T + 1) / 2;
+    part = groups > 0 ? a.template take<int32_t>((size_t)groups * N * tri * kIT * kIT) : nullptr;
+  }
+};
+}  // namespace
+
 extern "C" size_t d2mi_solo_matrix_nms_workspace_size(int N, int k) {
-  WorkspaceSizer z;
-  z.take<int32_t>((size_t)N * k * k);
-  z.take<float>((size_t)N * k);
-  // (the MFMA path's partial tiles, sized for the most groups any P gives)
+  // sized for the most groups any P gives (solo_mfma_groups)
   const int T = (k + kIT - 1) / kIT, tri = T * (T + 1) / 2;
-  const int gmax = std::max(1, 256 / std::max(1, N * tri));
-  z.take<int32_t>((size_t)gmax * N * tri * kIT * kIT);
-  return z.off;
+  return layout_bytes<SoloNmsSpace>(N, k, std::max(1, 256 / std::max(1, N * tri)));
 }
 
 extern "C" int d2mi_solo_matrix_nms(const uint64_t* mask_bits, const int64_t* classes,
@@ -1157,19 +1176,18 @@ extern "C" int d2mi_solo_matrix_nms(const uint64_t* mask_bits, const int64_t* cl
   const int W64 = (P + 63) / 64;
   hipStream_t st = as_stream(stream);
   Workspace w(workspace, workspace_bytes);
-  int32_t* inter = w.take<int32_t>((size_t)N * k * k);
-  float* comp = w.take<float>((size_t)N * k);
+  const int groups = tuning(kTuneSoloMfma) != 0 ? solo_mfma_groups(N, k, W64) : 0;
+  SoloNmsSpace o;
+  o.lay(w, N, k, groups);
+  int32_t *inter = o.inter, *part = o.part;
+  float* comp = o.comp;
   D2MI_REQUIRE(w.ok(), "SOLO Matrix-NMS workspace too small (%zu < %zu)", workspace_bytes, w.off);
   if (tuning(kTuneSoloMfma) != 0) {
     // (inter's bytes hold the transposed IoU matrix: float, N * k * k)
     float* iouT = reinterpret_cast<float*>(inter);
     const int T = (k + kIT - 1) / kIT, tri = T * (T + 1) / 2;
-    const int groups = solo_mfma_groups(N, k, W64);
     const int slices = groups * kIWaves;
     const int wpw = ((W64 + slices - 1) / slices + kIWords - 1) / kIWords * kIWords;
-    int32_t* part = w.take<int32_t>((size_t)groups * N * tri * kIT * kIT);
-    D2MI_REQUIRE(w.ok(), "SOLO Matrix-NMS workspace too small (%zu < %zu)", workspace_bytes,
-                 w.off);
     // tuning "solo_mfma": 2 (default) = bits expanded by an LDS table (r6:
     // intersections 38.1 -> 31.9 us per call, profiles/r6m_stats_*.csv), 1 = by
     // arithmetic
@@ -1210,11 +1228,20 @@ extern "C" int d2mi_solo_matrix_nms(const uint64_t* mask_bits, const int64_t* cl
   return 0;
 }
 
+namespace {
+struct FinalizeSpace {
+  int32_t* det_src;
+  BoxAcc* part;
+  template <typename A>
+  void lay(A& a, int N, int max_det, int OH) {
+    det_src = a.template take<int32_t>((size_t)N * max_det);
+    part = a.template take<BoxAcc>((size_t)N * max_det * ((OH + kPasteRows - 1) / kPasteRows));
+  }
+};
+}  // namespace
+
 extern "C" size_t d2mi_solo_finalize_workspace_size(int N, int max_det, int OH) {
-  WorkspaceSizer z;
-  z.take<int32_t>((size_t)N * max_det);
-  z.take<BoxAcc>((size_t)N * max_det * ((OH + kPasteRows - 1) / kPasteRows));
-  return z.off;
+  return layout_bytes<FinalizeSpace>(N, max_det, OH);
 }
 
 extern "C" int d2mi_solo_finalize(const float* nms_scores, const int64_t* top_classes,
@@ -1234,8 +1261,10 @@ extern "C" int d2mi_solo_finalize(const float* nms_scores, const int64_t* top_cl
   hipStream_t st = as_stream(stream);
   Workspace w(workspace, workspace_bytes);
   const int nparts = (OH + kPasteRows - 1) / kPasteRows;
-  int32_t* det_src = w.take<int32_t>((size_t)N * max_det);
-  BoxAcc* part = w.take<BoxAcc>((size_t)N * max_det * nparts);
+  FinalizeSpace o;
+  o.lay(w, N, max_det, OH);
+  int32_t* det_src = o.det_src;
+  BoxAcc* part = o.part;
   D2MI_REQUIRE(w.ok(), "SOLO finalize workspace too small (%zu < %zu)", workspace_bytes, w.off);
   hipLaunchKernelGGL(solo_keep_kernel, dim3(N), dim3(512), 0, st, nms_scores, top_classes,
                      top_count, k, update_thr, max_det, det_src, out_scores, out_classes,

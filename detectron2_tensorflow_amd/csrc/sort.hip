@@ -153,13 +153,18 @@ int merge_passes(int cap) {
   return n;
 }
 
+struct SortSpace {
+  uint64_t* tmp;  // the other ping-pong buffer
+  template <typename A>
+  void lay(A& a, int S, int cap) {
+    tmp = a.template take<uint64_t>((size_t)S * cap);
+  }
+};
+
 }  // namespace
 
 size_t sort_workspace_size(int S, int cap) {
-  if (cap <= kLdsSortCap) return 0;
-  WorkspaceSizer z;
-  z.take<uint64_t>((size_t)S * cap);  // the other ping-pong buffer
-  return z.off;
+  return cap <= kLdsSortCap ? 0 : layout_bytes<SortSpace>(S, cap);
 }
 
 int sort_keys_segmented(const uint64_t* keys_in, uint64_t* keys_out, const int32_t* lens, int S,
@@ -172,13 +177,14 @@ int sort_keys_segmented(const uint64_t* keys_in, uint64_t* keys_out, const int32
     return 0;
   }
   Workspace w(ws, ws_bytes);
-  uint64_t* tmp = w.take<uint64_t>((size_t)S * cap);
+  SortSpace o;
+  o.lay(w, S, cap);
   D2MI_REQUIRE(w.ok(), "sort workspace too small (%zu < %zu)", ws_bytes, w.off);
   const int nt = (cap + kTile - 1) / kTile;
   D2MI_REQUIRE((long long)S * nt < 65536, "segmented sort: %d segments x %d tiles too many", S, nt);
   // the passes alternate buffers; start so that the last one writes keys_out
   const int passes = merge_passes(cap);
-  uint64_t* bufs[2] = {keys_out, tmp};
+  uint64_t* bufs[2] = {keys_out, o.tmp};
   int cur = passes % 2;  // buffer the tile sort writes
   hipLaunchKernelGGL(rank_sort_tiles_kernel, dim3(kTile / kRankI, S * nt), dim3(kRankT),
                      kTile * sizeof(uint64_t), stream, keys_in, bufs[cur], lens, cap, kTile, nt);

@@ -702,17 +702,24 @@ __global__ __launch_bounds__(kThreads) void topk_floor_decide_kernel(
     st[s] = y;
   }
 }
+struct TopkSpace {
+  SegState* st;
+  uint32_t* hist;
+  uint64_t *candA, *candB, *fbuf;
+  template <typename A>
+  void lay(A& a, int S) {
+    st = a.template take<SegState>(S);
+    hist = a.template take<uint32_t>((size_t)S * kRep * kBins);
+    candA = a.template take<uint64_t>((size_t)S * kCap);
+    candB = a.template take<uint64_t>((size_t)S * kCap);
+    fbuf = a.template take<uint64_t>((size_t)S * kFloorSlots * kFloorSlotCap);
+  }
+};
 }  // namespace
 
 size_t topk_workspace_size(int S, int k) {
   (void)k;
-  WorkspaceSizer z;
-  z.take<SegState>(S);
-  z.take<uint32_t>((size_t)S * kRep * kBins);
-  z.take<uint64_t>((size_t)S * kCap);
-  z.take<uint64_t>((size_t)S * kCap);
-  z.take<uint64_t>((size_t)S * kFloorSlots * kFloorSlotCap);
-  return z.off;
+  return layout_bytes<TopkSpace>(S);
 }
 
 int topk_core_ex(const float* values, const int64_t* seg_start, const int32_t* seg_len,
@@ -723,11 +730,11 @@ int topk_core_ex(const float* values, const int64_t* seg_start, const int32_t* s
   D2MI_REQUIRE(key_mode == 0 || key_mode == 1, "key_mode must be 0 or 1");
   if (S == 0) return 0;
   Workspace w(ws, ws_bytes);
-  SegState* st = w.take<SegState>(S);
-  uint32_t* hist = w.take<uint32_t>((size_t)S * kRep * kBins);
-  uint64_t* candA = w.take<uint64_t>((size_t)S * kCap);
-  uint64_t* candB = w.take<uint64_t>((size_t)S * kCap);
-  uint64_t* fbuf = w.take<uint64_t>((size_t)S * kFloorSlots * kFloorSlotCap);
+  TopkSpace o;
+  o.lay(w, S);
+  SegState* st = o.st;
+  uint32_t* hist = o.hist;
+  uint64_t *candA = o.candA, *candB = o.candB, *fbuf = o.fbuf;
   D2MI_REQUIRE(w.ok(), "top-k workspace too small (%zu < %zu)", ws_bytes, w.off);
   // chunk per workgroup: 16 K elements for the dense RetinaNet levels, 4 K
   // for RPN-sized segments (more workgroups over a smaller scan)

@@ -45,3 +45,124 @@ def test_host_side_argument_errors_raise_without_gpu():
     rc = lib.d2mi_conv2d_nhwc(None, None, None, None, None, None, 1, 8, 8, 3, 16, 3, 3, 1, 1, 1,
                               0, None)
     assert rc < 0 and "multiple of 4" in _C.last_error()
+
+
+def _short_workspace_calls(lib):
+    """(name, queried size, call taking workspace_bytes) of ops whose host code
+    reaches the workspace carve before any HIP call or pointer dereference."""
+    ws = ctypes.c_void_p(256)  # non-null, never dereferenced: the carve is refused first
+    return [
+        ("nms", lib.d2mi_nms_workspace_size(3, 100),
+         lambda n: lib.d2mi_nms(None, None, None, 3, 100, 10, 0.5, None, None, ws, n, None)),
+        ("group_norm", lib.d2mi_group_norm_workspace_size(2, 8, 8, 32, 4),
+         lambda n: lib.d2mi_group_norm_nhwc(None, 2, 8, 8, 32, 4, None, None, 1e-5, 0, 0, 0, None,
+                                            ws, n, None)),
+        ("fast_rcnn", lib.d2mi_fast_rcnn_workspace_size(2, 16, 3, 0.05, 10),
+         lambda n: lib.d2mi_fast_rcnn_inference(None, None, None, None, None, 0, 2, 16, 3, 0, None,
+                                                None, 4.135, 0.05, 0.5, 10, None, None, None,
+                                                None, None, ws, n, None)),
+        ("topk", lib.d2mi_topk_workspace_size(3, 65),
+         lambda n: lib.d2mi_topk(None, None, None, 3, 1000, 65, 0, None, None, None, ws, n, None)),
+        ("matrix_nms", lib.d2mi_matrix_nms_workspace_size(65),
+         lambda n: lib.d2mi_matrix_nms(None, None, None, None, 65, 64, 0, 2.0, None, ws, n, None)),
+        ("solo_finalize", lib.d2mi_solo_finalize_workspace_size(2, 5, 65),
+         lambda n: lib.d2mi_solo_finalize(None, None, None, None, 2, 4, 8, 8, 0.05, 5, 0.5, 65, 16,
+                                          None, None, None, None, None, ws, n, None)),
+    ]
+
+
+def test_workspace_one_byte_short_is_refused_without_gpu():
+    """Every op lays its workspace out with the function its *_workspace_size
+    runs: one byte less than the queried size is refused on the host."""
+    from detectron2_tensorflow_amd import _C
+    lib = _C.load()
+    for name, size, call in _short_workspace_calls(lib):
+        assert size > 1, name
+        rc = call(size - 1)
+        msg = _C.last_error()
+        assert rc < 0 and "too small" in msg and f"{size - 1} < {size}" in msg, (name, rc, msg)
+
+
+def test_parsed_signatures_match_the_header():
+    """The ctypes table is parsed from include/d2mi.h; one literal entry per type class."""
+    from detectron2_tensorflow_amd import _C
+    c = ctypes
+    P, I, F, Z = c.c_void_p, c.c_int, c.c_float, c.c_size_t
+    want = {
+        "d2mi_nms": (I, [P, P, P, I, I, I, F, P, P, P, Z, P]),
+        "d2mi_subsample": (I, [P, I, I, c.c_longlong, I, I, P, P, P, P, P, I, P, Z, P]),
+        "d2mi_split_bf16x3": (I, [P, c.c_int64, P, P]),
+        "d2mi_source_hash": (c.c_char_p, []),
+        "d2mi_roi_align_bwd_workspace_size": (Z, [P, I, I, I, I, I, I]),
+        "d2mi_error_word_dev": (P, []),
+        "d2mi_set_tuning": (I, [c.c_char_p, I]),
+    }
+    sigs = _C.parse_header(open(os.path.join(ROOT, "include", "d2mi.h")).read())
+    assert tuple(sigs) == _C.EXPORTED
+    lib = _C.load()
+    for name, (res, args) in want.items():
+        assert sigs[name][0] is res and len(sigs[name][1]) == len(args), name
+        assert all(a is b for a, b in zip(sigs[name][1], args)), name
+        fn = getattr(lib, name)  # and load() put them on the functions
+        assert fn.restype is res and list(fn.argtypes) == args, name
+
+
+def test_parser_refuses_a_type_it_does_not_know():
+    import pytest
+    from detectron2_tensorflow_amd import _C
+    ok = "int d2mi_a(const float* x, int n);\nsize_t d2mi_b(void);\n"
+    assert _C.parse_header(ok) == {"d2mi_a": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+                                   "d2mi_b": (ctypes.c_size_t, [])}
+    for bad in ("int d2mi_c(double x);", "int d2mi_c(unsigned n);", "short d2mi_c(int n);",
+                "int d2mi_c(my_handle_t h);", "int d2mi_c(int);"):
+        with pytest.raises(TypeError):
+            _C.parse_header(ok + bad)
+
+
+TUNING_DEFAULTS = {
+    "conv_ws": 2, "roi_fwd": -1, "wgrad_ws": 1, "conv_epi": 1, "wgrad_ws1": 6, "wgrad_xcd": 1,
+    "conv_xcd": 1, "wgrad_inc": 1, "conv_ws_mink": 16, "roi_pix_grid": 8192, "conv_stream": 8192,
+    "roi_bwd_rec": 1, "retina_fused": 1, "rpn_merge": 1, "nms_scan": 1, "roi_heavy": 16,
+    "rpn_compact": 1, "conv_stream_nt": 2, "conv_nt": 0, "conv_tail_mink": 8,
+    "conv_ws_mintiles": 0, "sgd_rev": 0, "retina_rank": 0, "solo_mfma": 2, "retina_var": 12018,
+}
+
+_TUNING_CHILD = """
+import json, sys
+from detectron2_tensorflow_amd import _C
+from detectron2_tensorflow_amd.layers import ops
+out = {k: ops.get_tuning(k) for k in json.loads(sys.argv[1])}
+out["<unknown get>"] = _C.lib().d2mi_get_tuning(b"no_such_knob")
+try:
+    ops.set_tuning("no_such_knob", 1)
+    out["<unknown set>"] = "accepted"
+except _C.D2MIError as e:
+    out["<unknown set>"] = str(e)
+print(json.dumps(out))
+"""
+
+
+def _tuning_in_child(extra_env):
+    """get_tuning of every knob in a fresh process whose only D2MI_* variables are extra_env."""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if not k.startswith("D2MI_")}
+    env.update(extra_env, PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, "-c", _TUNING_CHILD, json.dumps(list(TUNING_DEFAULTS))],
+                       env=env, capture_output=True, text=True, cwd=ROOT)
+    assert r.returncode == 0, r.stderr
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def test_tuning_defaults_and_environment_without_gpu():
+    """The 25 knobs' defaults, their D2MI_<KEY> environment variables, and unknown keys."""
+    from detectron2_tensorflow_amd import _build
+    _build.build()
+    got = _tuning_in_child({})
+    assert got.pop("<unknown get>") == -2 ** 31
+    assert "unknown tuning key" in got.pop("<unknown set>")
+    assert got == TUNING_DEFAULTS
+    got = _tuning_in_child({"D2MI_CONV_NT": "1", "D2MI_RETINA_VAR": "0"})
+    assert got.pop("<unknown get>") == -2 ** 31 and "unknown tuning key" in got.pop("<unknown set>")
+    assert got == dict(TUNING_DEFAULTS, conv_nt=1, retina_var=0)
