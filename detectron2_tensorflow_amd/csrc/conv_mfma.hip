@@ -42,6 +42,7 @@
 // f32-class error (tests: error vs float64 within a small factor of the
 // native f32 path's).
 #include "common.h"
+#include "conv_plan.h"
 #include "internal.h"
 
 #include <mutex>
@@ -52,8 +53,7 @@ namespace {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
-constexpr int BK = 32, LDSP = 36, LDSB = 32;
-constexpr int kMaxConvLevels = 6;
+constexpr int BK = kConvBK, LDSP = 36, LDSB = 32;
 
 // bf16 LDS images: 64-B rows (32 bf16 = one BK step) whose four 16-B chunks
 // are XOR-swizzled by (row >> 2) & 3.  ds_read_b128 phases (lanes
@@ -110,7 +110,7 @@ struct ConvArgs {
   int M, nM, nN, ntiles, splits, kt_per_split, nk, cchunks;
   // this launch covers tiles [tile_base, tile_base + ntiles); split-K
   // partials cover output rows [m_base, m_end) (a main launch and a tail launch
-  // last round would run mostly empty, see conv_core)
+  // last round would run mostly empty, see plan_conv)
   int tile_base, m_base, m_end;
   int lds_epi;  // store_outputs_lds usable (Cout % 4 == 0, 16-B aligned operands)
   int nt_store;  // final outputs of the LDS epilogue / split-K reduce stored non-temporally
@@ -1423,29 +1423,9 @@ __global__ __launch_bounds__(256) void pack_weights_many_kernel(PackMany p) {
     if (co0 + j < Cout) out[((size_t)tap * Cout + co0 + j) * Cin + ci0 + lane] = tile[lane][j];
 }
 
-struct Plan {
-  int cfg;  // 0: 128x128, 1: 128x64, 2: 128x32
-  int BM, BN, splits, kt_per_split, nk, ntiles;
-  // tail split: the first full_tiles run as whole tiles, the remaining
-  // tail_tiles (whole pixel-row blocks) split K tail_splits ways
-  int full_tiles, tail_tiles, tail_splits, tail_kt_per_split;
-  int main_m_end;  // output rows of the main launch (its split-K partial rows)
-  size_t ws_bytes;
-};
-
-// Resident workgroups of the 128-wide conv tiles: 2 per CU.
-// Resident workgroups per CU of a plan's kernel: the 128x128 split kernel
-// runs three (168 VGPRs, 48 KiB LDS: conv_mfma_kernel<..., OCC = 3>), the
-// others two.  D2MI_CONV_OCC=2 keeps the 128x128 split kernel at two (A/B).
-static bool occ3_enabled() {
-  static const int on = [] {
-    const char* e = getenv("D2MI_CONV_OCC");
-    return !(e && e[0] == '2');
-  }();
-  return on;
-}
-
-static int wg_slots(int cfg) {
+// The device's CU count for the planners (conv_plan.h); without a device 256,
+// the MI355X value: a plan query there answers as the GPU machine plans.
+static int device_cus() {
   static int cus = 0;
   if (cus == 0) {
     int dev = 0, c = 0;
@@ -1455,93 +1435,18 @@ static int wg_slots(int cfg) {
       c = 256;  // MI355X
     cus = c;
   }
-  if (cfg == 3) return cus;  // the warp-specialised kernel: one per CU
-  return (cfg == 0 && occ3_enabled() ? 3 : 2) * cus;
+  return cus;
 }
 
-// wide_ok: the 128x128 tile may be used -- its kernels only carry the LDS
-// epilogue (Cout % 4 == 0 and 16-B aligned operands); otherwise 128x64.
-// split: the split-product math (kSplit3); cfg 3 (the warp-specialised
-// 256x128 kernel, tuning "conv_ws") exists only in that form, and takes the
-// long-K convs (>= 16 k-steps: every 3x3 with Cin >= 64, the 1x1s with
-// Cin >= 512), where its deeper staging pipeline pays; the short-K 1x1s
-// (2-8 k-steps) stay on the 3-per-CU kernel, whose prologue / epilogue
-// overlap across workgroups (tools/ws_ab.py, 16 Mask R-CNN shapes).
-// The stride-1 1x1 shapes with K = 256 that the streaming kernel takes
-// (stream1x1_variant: 1.17x into 64 channels, 1.12x into 512 at >= 32 k
-// pixels, profiles/r5_stream_ab_force_tn_rule.log); the tiled plan of these
-// shapes never splits its tail tiles' K, so both kernels round alike.
-static bool stream256_shape(int M, int Cout, int KH, int KW, int Cin) {
-  return KH == 1 && KW == 1 && Cin == 256 && M >= 32768 && (Cout <= 64 || Cout == 512) &&
-         Cout % 4 == 0;
-}
-
-Plan make_plan(int M, int Cout, int KH, int KW, int Cin, bool wide_ok, bool split = true) {
-  Plan p;
-  p.cfg = Cout <= 32 ? 2 : (Cout <= 64 || !wide_ok ? 1 : 0);
-  // tuning "conv_ws_mink": the fewest k-steps that go to the WS kernel (A/B)
-  if (p.cfg == 0 && split && tuning(kTuneConvWS) > 0 &&
-      KH * KW * ((Cin + BK - 1) / BK) >= tuning(kTuneConvWSMinK) &&
-      KH * KW <= 32 &&  // (the WS stagers keep a 32-bit tap mask per row)
-      // (tuning "conv_ws_mintiles": the fewest 256x128 tiles that go to the WS kernel, A/B)
-      ((M + 255) / 256) * ((Cout + 127) / 128) >= tuning(kTuneConvWSMinTiles))
-    p.cfg = 3;
-  p.BM = p.cfg == 3 ? 256 : 128;
-  p.BN = (p.cfg == 0 || p.cfg == 3) ? 128 : (p.cfg == 1 ? 64 : 32);
-  const int nM = (M + p.BM - 1) / p.BM, nN = (Cout + p.BN - 1) / p.BN;
-  p.ntiles = nM * nN;
-  p.nk = KH * KW * ((Cin + BK - 1) / BK);
-  p.splits = 1;
-  const int G = wg_slots(p.cfg);
-  // Fewer tiles than resident workgroups and a long K: split K (to about
-  // GS workgroups: every split writes and the reduce reads one more partial
-  // slab of the output).
-  static const int GS = [] {
-    const char* e = getenv("D2MI_CONV_SPLIT_SLOTS");
-    return e ? atoi(e) : 0;
-  }();
-  // target: two workgroups per CU even for the 3-per-CU kernel (A/B over
-  // 384..1024 slots on the training step: 512 fastest, +2.5 % over 768 -- fewer
-  // splits, less partial-slab traffic for the reduce)
-  const int gs = GS > 0 ? GS : (p.cfg == 3 ? wg_slots(3) : wg_slots(1));
-  if (4 * p.ntiles < 3 * gs && p.nk >= 16) {
-    p.splits = std::min(std::max(1, gs / p.ntiles), std::min(p.nk / 8, 16));
-  }
-  p.kt_per_split = (p.nk + p.splits - 1) / p.splits;
-  p.splits = (p.nk + p.kt_per_split - 1) / p.kt_per_split;
-  p.ws_bytes = p.splits > 1 ? (size_t)p.splits * M * Cout * sizeof(float) : 0;
-  // Tail split: with more tiles than resident workgroups, a last round that
-  // is mostly empty (1050 tiles = 2 rounds of 512 + 26 on the FPN p2 3x3,
-  // 525 = 512 + 13 on p3) costs about a whole round for a few tiles.  Those
-  // tiles (whole pixel-row blocks) are split along K over the idle slots
-  // instead and reduced in a fixed order.
-  p.full_tiles = p.ntiles;
-  p.tail_tiles = 0;
-  p.tail_splits = 1;
-  p.tail_kt_per_split = p.nk;
-  p.main_m_end = M;
-  static const char* tail_env = getenv("D2MI_CONV_TAIL");  // "0": no tail split (A/B)
-  // (tuning "conv_tail_mink": the fewest k-steps whose tail tiles are split, A/B)
-  if (p.splits == 1 && p.ntiles > G && p.nk >= std::max(2, tuning(kTuneConvTailMinK)) &&
-      !(tail_env && tail_env[0] == '0') &&
-      !stream256_shape(M, Cout, KH, KW, Cin)) {
-    const int full = (p.ntiles / G) * G / nN * nN;
-    const int tail = p.ntiles - full;
-    if (tail > 0 && 2 * tail <= G) {
-      int S = std::min(std::min(G / tail, p.nk / 4), 32);
-      if (S >= 2) {
-        const int kps = (p.nk + S - 1) / S;
-        S = (p.nk + kps - 1) / kps;
-        p.full_tiles = full;
-        p.tail_tiles = tail;
-        p.tail_splits = S;
-        p.tail_kt_per_split = kps;
-        const int m_base = full / nN * p.BM;
-        p.ws_bytes = (size_t)S * (M - m_base) * Cout * sizeof(float);
-      }
-    }
-  }
-  return p;
+// PlanOperands of a launch's pointers (a null pointer counts as aligned).
+static int plan_operands(const void* topdown, const void* residual, const void* gate,
+                         const void* y, const void* bias, const void* workspace) {
+  auto al16 = [](uintptr_t q) { return (q & 15) == 0; };
+  return (topdown ? kOpTopdown : 0) | (residual ? kOpResidual : 0) | (gate ? kOpGate : 0) |
+         (al16((uintptr_t)y | (uintptr_t)topdown | (uintptr_t)residual | (uintptr_t)gate)
+              ? kOpAligned : 0) |
+         (al16((uintptr_t)bias) ? kOpBiasAligned : 0) | (workspace ? kOpWorkspace : 0) |
+         (al16((uintptr_t)workspace) ? kOpWsAligned : 0);
 }
 
 }  // namespace
@@ -1601,104 +1506,39 @@ extern "C" int d2mi_conv_pack_weights(const float* w_hwio, int KH, int KW, int C
   return 0;
 }
 
+// The tiled kernel of a plan (conv_plan.h: family, resident workgroups).
 // D2MI_CONV_WS / d2mi_set_tuning("conv_ws", d): the warp-specialised
-// 256x128 split kernel (conv_ws_kernel, plan cfg 3): 0 off, > 0 on.  r3: a
+// 256x128 split kernel (conv_ws_kernel): 0 off, > 0 on.  r3: a
 // 16-deep, 3/4-stage read-ahead variant measured bit-identical but slower;
 // r4 removed the other measured-slower A/B forms (stream-K, the in-launch
 // split-K fix-up, the multi-level WS launch, the pre-split-plane kernel) --
 // DESIGN section 5 keeps their numbers.
-
-template <bool SPLIT>
-static void launch_conv(int cfg, bool db, dim3 grid, hipStream_t st, const ConvArgs& a) {
-  if (cfg == 3) {  // the warp-specialised 256x128 split kernel (plan cfg 3)
+// 128x128 tiles: single-buffered LDS (two barriers per k-step, 3 workgroups
+// per CU) measured faster than double-buffered on every Mask R-CNN shape,
+// f32 and split, large grids and small.
+// ML: the multi-level launches (ConvArgs::nlev > 0).
+template <bool SPLIT, bool ML>
+static void launch_conv(int family, int occ, dim3 grid, hipStream_t st, const ConvArgs& a) {
+  if (family == kConvWS256x128) {
     // (LD = 3 does not fit the 128-VGPR budget of 4 waves per SIMD: it spills)
-    if constexpr (SPLIT) hipLaunchKernelGGL((conv_ws_kernel<2>), grid, dim3(1024), 0, st, a);
-    return;
-  }
-  if (cfg == 0 && !db && occ3_enabled()) {
-    hipLaunchKernelGGL((conv_mfma_kernel<2, 2, 2, 2, false, SPLIT, 3>), grid, dim3(256), 0, st, a);
-    return;
-  }
-  if (cfg == 0) {
-    if (db)
-      hipLaunchKernelGGL((conv_mfma_kernel<2, 2, 2, 2, true, SPLIT>), grid, dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((conv_mfma_kernel<2, 2, 2, 2, false, SPLIT>), grid, dim3(256), 0, st, a);
-  } else if (cfg == 1) {
-    hipLaunchKernelGGL((conv_mfma_kernel<4, 1, 1, 2, true, SPLIT>), grid, dim3(256), 0, st, a);
-  } else {
-    hipLaunchKernelGGL((conv_mfma_kernel<4, 1, 1, 1, true, SPLIT>), grid, dim3(256), 0, st, a);
-  }
-}
-
-// Multi-level launches (ConvArgs::nlev > 0): no split-K, single-buffered.
-template <bool SPLIT>
-static void launch_conv_levels(int cfg, dim3 grid, hipStream_t st, const ConvArgs& a) {
-  if (cfg == 0) {
-    if (occ3_enabled())
-      hipLaunchKernelGGL((conv_mfma_kernel<2, 2, 2, 2, false, SPLIT, 3, true>), grid, dim3(256), 0,
-                         st, a);
-    else
-      hipLaunchKernelGGL((conv_mfma_kernel<2, 2, 2, 2, false, SPLIT, 2, true>), grid, dim3(256), 0,
-                         st, a);
-  } else if (cfg == 1) {
-    hipLaunchKernelGGL((conv_mfma_kernel<4, 1, 1, 2, true, SPLIT, 2, true>), grid, dim3(256), 0, st,
+    if constexpr (SPLIT && !ML) hipLaunchKernelGGL((conv_ws_kernel<2>), grid, dim3(1024), 0, st, a);
+  } else if (family == kConv128x128 && occ == 3) {
+    hipLaunchKernelGGL((conv_mfma_kernel<2, 2, 2, 2, false, SPLIT, 3, ML>), grid, dim3(256), 0, st,
+                       a);
+  } else if (family == kConv128x128) {
+    hipLaunchKernelGGL((conv_mfma_kernel<2, 2, 2, 2, false, SPLIT, 2, ML>), grid, dim3(256), 0, st,
+                       a);
+  } else if (family == kConv128x64) {
+    hipLaunchKernelGGL((conv_mfma_kernel<4, 1, 1, 2, true, SPLIT, 2, ML>), grid, dim3(256), 0, st,
                        a);
   } else {
-    hipLaunchKernelGGL((conv_mfma_kernel<4, 1, 1, 1, true, SPLIT, 2, true>), grid, dim3(256), 0, st,
+    hipLaunchKernelGGL((conv_mfma_kernel<4, 1, 1, 1, true, SPLIT, 2, ML>), grid, dim3(256), 0, st,
                        a);
   }
-}
-
-static int conv_dims(int H, int W, int KH, int KW, int stride, int pb, int pe, int& OH, int& OW) {
-  OH = (H + pb + pe - KH) / stride + 1;
-  OW = (W + pb + pe - KW) / stride + 1;
-  return (OH > 0 && OW > 0) ? 0 : -1;
-}
-
-extern "C" size_t d2mi_conv2d_workspace_size(int N, int H, int W, int Cin, int Cout, int KH,
-                                             int KW, int stride, int pad_beg, int pad_end) {
-  int OH, OW;
-  if (conv_dims(H, W, KH, KW, stride, pad_beg, pad_end, OH, OW)) return 0;
-  const Plan p = make_plan(N * OH * OW, Cout, KH, KW, Cin, Cout % 4 == 0);
-  return p.ws_bytes;
-}
-
-// conv1x1_stream_kernel's variant for a launch (0: not eligible): stride-1
-// unpadded 1x1, split products, no top-down, Cin 64 / 128 / 256, Cout % 4
-// == 0, 16-B aligned operands, and enough pixel strips to fill the chip
-// (tuning "conv_stream": 0 off; else the fewest output pixels).
-static int stream1x1_variant(const ConvArgs& a, const Plan& p, int flags) {
-  const int tv = tuning(kTuneConvStream);
-  const bool force = tv < 0;  // (A/B: every eligible shape of >= -tv pixels)
-  const int minM = force ? -tv : tv;
-  if (tv == 0 || !(flags & kSplit3) || a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0 ||
-      a.topdown || !(a.Cin == 64 || a.Cin == 128 || a.Cin == 256) || a.M < minM)
-    return 0;
-  auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-  if (a.Cout % 4 != 0 || !al16(a.x) || !al16(a.w) || !al16(a.y) || !al16(a.residual) ||
-      !al16(a.gate) || !al16(a.bias))
-    return 0;
-  if (a.Cin == 256 && a.residual && a.gate) return 0;  // (its registers spill)
-  // where it measured faster than the tiled kernel (tools/stream_ab.py,
-  // profiles/r5_stream_ab_force_tn_rule.log, with TN 2 when 128-wide slices
-  // leave too few strip tasks): every K = 64 and K = 128 launch.  K = 256
-  // (1.12-1.17x into <= 64 or 512 channels) only under force: the tiled
-  // kernel splits the K of its tail tiles there (>= 8 k-steps), so the two
-  // kernels' results differ in the last bit, and a launch whose operands
-  // are not 16-B aligned (a gradient bucket view) would then round
-  // differently from an aligned one (tests/test_gpu_dp.py's one-rank RCCL
-  // equality).  For K <= 128 both kernels sum in the same order: bit-identical.
-  if (a.Cin == 64 || a.Cin == 128) return a.Cin == 64 ? 1 : 2;
-  // r5b: K = 256 into <= 64 or 512 channels (where it wins) -- make_plan
-  // keeps those shapes' tiles whole (no tail split, stream256_shape), so the
-  // tiled fallback sums K in the stream kernel's order: bit-identical again
-  if (force || stream256_shape(a.M, a.Cout, a.KH, a.KW, a.Cin)) return 3;
-  return 0;
 }
 
 template <int TN, int KMAX>
-static void launch_stream1x1_t(dim3 grid, hipStream_t st, const ConvArgs& a, int nslices) {
+static void launch_stream1x1_t(const ConvPlan& p, hipStream_t st, const ConvArgs& a) {
   // tuning "conv_stream_nt": bit 0 streaming loads of the epilogue operands, bit 1
   // streaming (non-temporal) stores of the output -- default 2: the stores
   // alone (tools/stream_ab.py --nt, profiles/r5_stream_nt_*.log: 64 -> 256 +
@@ -1706,70 +1546,104 @@ static void launch_stream1x1_t(dim3 grid, hipStream_t st, const ConvArgs& a, int
   // lose on 128 -> 512; in-step -0.20 %, profiles/r5_ab_stream_nt.log)
   const int nt = tuning(kTuneConvStreamNt);
   constexpr int W = 8;
-  const bool r = a.residual != nullptr, g = a.gate != nullptr;
-  if (r && g) {
-    if constexpr (TN == 2)  // (both operands' registers: BN 64, launch_stream1x1)
+  const dim3 grid(p.grid);
+  if (p.form == 3) {
+    if constexpr (TN == 2)  // (both operands' registers: BN 64, plan_conv)
       hipLaunchKernelGGL((conv1x1_stream_kernel<TN, KMAX, W, true, true>), grid, dim3(64 * W), 0,
-                         st, a, nslices, nt);
-  } else if (r) {
+                         st, a, p.nslices, nt);
+  } else if (p.form == 1) {
     hipLaunchKernelGGL((conv1x1_stream_kernel<TN, KMAX, W, true, false>), grid, dim3(64 * W), 0,
-                       st, a, nslices, nt);
-  } else if (g) {
+                       st, a, p.nslices, nt);
+  } else if (p.form == 2) {
     hipLaunchKernelGGL((conv1x1_stream_kernel<TN, KMAX, W, false, true>), grid, dim3(64 * W), 0,
-                       st, a, nslices, nt);
+                       st, a, p.nslices, nt);
   } else {
     hipLaunchKernelGGL((conv1x1_stream_kernel<TN, KMAX, W, false, false>), grid, dim3(64 * W), 0,
-                       st, a, nslices, nt);
+                       st, a, p.nslices, nt);
   }
 }
 
-// variant: 1 K = 64, 2 K = 128, 3 K = 256.  BN 128 (TN 4) for K <= 128 with
-// at most one epilogue operand, else BN 64 (TN 2): the registers of a
-// residual AND a gate, and K = 256's A fragments, leave no room for TN 4.
-static int launch_stream1x1(int variant, const ConvArgs& a, void* stream) {
-  constexpr int WAVES = 8;
-  const bool both = a.residual && a.gate;
-  // TN 2 also when 128-wide slices leave fewer strip tasks than the chip has
-  // waves (one 8-wave workgroup per CU)
-  const int strips = (a.M + 31) / 32;
-  const bool few = (long long)strips * ((a.Cout + 127) / 128) < 8LL * wg_slots(3);
-  const int TN = (variant == 3 || both || few) ? 2 : 4;
-  const int BN = 32 * TN;
-  const int nslices = (a.Cout + BN - 1) / BN;
-  const int nstrips = (a.M + 31) / 32;
-  // one resident workgroup per CU (LDS: the weight slice + the slabs) over
-  // all slices, whole XCD rounds, and no group without a strip for each of
-  // its waves
-  int groups = std::max(1, wg_slots(3) / nslices / 8);
-  groups = std::min(groups, std::max(1, nstrips / WAVES / 8));
-  const dim3 grid(8 * groups * nslices);
-  hipStream_t st = as_stream(stream);
-  if (variant == 1 && TN == 4)
-    launch_stream1x1_t<4, 64>(grid, st, a, nslices);
-  else if (variant == 1)
-    launch_stream1x1_t<2, 64>(grid, st, a, nslices);
-  else if (variant == 2 && TN == 4)
-    launch_stream1x1_t<4, 128>(grid, st, a, nslices);
-  else if (variant == 2)
-    launch_stream1x1_t<2, 128>(grid, st, a, nslices);
+static void launch_stream1x1(const ConvPlan& p, hipStream_t st, const ConvArgs& a) {
+  if (p.kmax == 64 && p.tn == 4)
+    launch_stream1x1_t<4, 64>(p, st, a);
+  else if (p.kmax == 64)
+    launch_stream1x1_t<2, 64>(p, st, a);
+  else if (p.kmax == 128 && p.tn == 4)
+    launch_stream1x1_t<4, 128>(p, st, a);
+  else if (p.kmax == 128)
+    launch_stream1x1_t<2, 128>(p, st, a);
   else
-    launch_stream1x1_t<2, 256>(grid, st, a, nslices);
-  D2MI_LAUNCH_CHECK();
+    launch_stream1x1_t<2, 256>(p, st, a);
+}
+
+// What every f32-operand conv entry point and d2mi_conv2d_plan refuse.
+static int conv_check_shape(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride) {
+  D2MI_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0,
+               "bad conv shape");
+  D2MI_REQUIRE(Cin % 4 == 0, "Cin must be a multiple of 4 (got %d)", Cin);
+  D2MI_REQUIRE((int64_t)H * W * Cin * sizeof(float) < (1ll << 31),
+               "one conv input image must be < 2 GiB");
+  D2MI_REQUIRE((int64_t)KH * KW * Cin * Cout * sizeof(float) < (1ll << 31),
+               "conv weights must be < 2 GiB");
   return 0;
+}
+// Images per launch: a batch of >= 2 GiB goes in chunks (32-bit buffer offsets).
+static int conv_chunk(int N, int H, int W, int Cin) {
+  const int64_t img_bytes = (int64_t)H * W * Cin * sizeof(float);
+  return N * img_bytes >= (1ll << 31) ? (int)(((1ll << 31) - 1) / img_bytes) : N;
+}
+
+extern "C" size_t d2mi_conv2d_workspace_size(int N, int H, int W, int Cin, int Cout, int KH,
+                                             int KW, int stride, int pad_beg, int pad_end) {
+  // the split-product plan of 16-B aligned operands with all the workspace it asks for
+  ConvPlan p;
+  if (plan_conv({N, H, W, Cin, Cout, KH, KW, stride, pad_beg, pad_end}, kSplit3,
+                kOpAllAligned | kOpWorkspace, SIZE_MAX, device_cus(), &p))
+    return 0;
+  return p.ws_bytes;
+}
+
+// The plan as integers (include/d2mi.h lists the fields).
+extern "C" int d2mi_conv2d_plan(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                                int pad_beg, int pad_end, int flags, int operands,
+                                size_t workspace_bytes, int32_t* out, int out_len) {
+  D2MI_REQUIRE((flags & ~31) == 0 && (operands & ~127) == 0, "conv plan: unknown flag or operand bits");
+  if (conv_check_shape(N, H, W, Cin, Cout, KH, KW, stride)) return -1;
+  if (flags & kMaskByResidual)  // (the residual operand is the gate, d2mi_conv2d_nhwc_ex)
+    operands = (operands & ~(kOpResidual | kOpGate)) | (operands & kOpResidual ? kOpGate : 0);
+  ConvPlan p;
+  D2MI_REQUIRE(plan_conv({std::min(N, conv_chunk(N, H, W, Cin)), H, W, Cin, Cout, KH, KW, stride,
+                          pad_beg, pad_end},
+                         flags, operands, workspace_bytes, device_cus(), &p) == 0,
+               "conv output is empty");
+  const ConvLaunch &m = p.main, &t = p.tail;
+  const int32_t v[] = {p.family, p.occ, p.split3, p.lds_epi, p.M, p.BM, p.BN, p.nM, p.nN, p.nk,
+                       m.tile0, m.tiles, m.splits, m.kt_per_split, m.m_base, m.m_end, m.reduce,
+                       m.reduce_grid, t.tile0, t.tiles, t.splits, t.kt_per_split, t.m_base, t.m_end,
+                       t.reduce, t.reduce_grid, p.kmax, p.tn, p.form, p.nslices, p.grid,
+                       (int32_t)(p.ws_bytes & 0x7fffffff), (int32_t)(p.ws_bytes >> 31)};
+  return emit_plan(v, (int)(sizeof(v) / sizeof(v[0])), out, out_len);
 }
 
 // Shared launcher of the f32-operand convs (the split or native-f32 MFMA
-// products, flags bit 2).
+// products, flags bit 2): fill ConvArgs from the plan, launch its kernels.
 static int conv_core(const float* x, const float* w_packed, const float* bias,
                      const float* topdown, const float* residual, const float* gate, float* y,
                      int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
                      int pad_beg, int pad_end, int flags, void* workspace,
                      size_t workspace_bytes, void* stream) {
+  ConvPlan p;
+  D2MI_REQUIRE(plan_conv({N, H, W, Cin, Cout, KH, KW, stride, pad_beg, pad_end}, flags,
+                         plan_operands(topdown, residual, gate, y, bias, workspace),
+                         workspace_bytes, device_cus(), &p) == 0,
+               "conv output is empty");
+  ConvSpace sp;
+  Workspace carve(workspace, workspace_bytes);
+  sp.lay(carve, p, Cout);
   ConvArgs a = {};
   a.x = x;
-  const int64_t xe = (int64_t)N * H * W * Cin, we = (int64_t)KH * KW * Cin * Cout;
-  a.x_bytes = (int)(xe * 4);
-  a.w_bytes = (int)(we * 4);
+  a.x_bytes = (int)((int64_t)N * H * W * Cin * 4);
+  a.w_bytes = (int)((int64_t)KH * KW * Cin * Cout * 4);
   a.w = w_packed;
   a.bias = bias;
   a.topdown = topdown;
@@ -1785,60 +1659,29 @@ static int conv_core(const float* x, const float* w_packed, const float* bias,
   a.KW = KW;
   a.stride = stride;
   a.pad = pad_beg;
-  D2MI_REQUIRE(conv_dims(H, W, KH, KW, stride, pad_beg, pad_end, a.OH, a.OW) == 0,
-               "conv output is empty");
+  a.OH = p.OH;
+  a.OW = p.OW;
   a.flags = flags;
-  a.M = N * a.OH * a.OW;
-  {
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    a.lds_epi = Cout % 4 == 0 && al16(y) && al16(residual) && al16(gate) && al16(topdown) &&
-                al16(workspace);
-  }
+  a.M = p.M;
+  a.lds_epi = p.lds_epi;
   a.reg_partials = tuning(kTuneConvEpi) != 0;
   a.xcd2 = tuning(kTuneConvXCD) != 0;
   a.nt_store = tuning(kTuneConvNt) != 0;  // (tuning "conv_nt", A/B)
-  Plan p = make_plan(a.M, Cout, KH, KW, Cin, a.lds_epi != 0, (flags & kSplit3) != 0);
-  if (p.ws_bytes > workspace_bytes || workspace == nullptr) {  // no workspace: no split-K
-    p.splits = 1;
-    p.kt_per_split = p.nk;
-    p.full_tiles = p.ntiles;
-    p.tail_tiles = 0;
-    p.main_m_end = a.M;
-  }
-  a.nM = (a.M + p.BM - 1) / p.BM;
-  a.nN = (Cout + p.BN - 1) / p.BN;
-  a.ntiles = p.full_tiles;
-  a.tile_base = 0;
-  a.m_base = 0;
-  a.m_end = p.main_m_end;
-  a.splits = p.splits;
-  a.kt_per_split = p.kt_per_split;
+  a.nM = p.nM;
+  a.nN = p.nN;
   a.nk = p.nk;
   a.cchunks = (Cin + BK - 1) / BK;
-  a.partial = p.splits > 1 ? (float*)workspace : nullptr;
   a.tdH = (a.OH + 1) / 2;
   a.tdW = (a.OW + 1) / 2;
+  a.ntiles = p.main.tiles;
+  a.m_end = p.main.m_end;
+  a.splits = p.main.splits;
+  a.kt_per_split = p.main.kt_per_split;
   hipStream_t st = as_stream(stream);
-  ConvArgs t = a;  // the tail launch (when planned)
-  if (p.tail_tiles > 0) {
-    t.tile_base = p.full_tiles;
-    t.ntiles = p.tail_tiles;
-    t.m_base = p.full_tiles / a.nN * p.BM;
-    t.m_end = a.M;
-    t.splits = p.tail_splits;
-    t.kt_per_split = p.tail_kt_per_split;
-    t.partial = (float*)workspace +
-                (p.splits > 1 ? (size_t)p.splits * p.main_m_end * Cout : (size_t)0);
-  }
-  // 128x128 tiles: single-buffered LDS (two barriers per k-step, 3 workgroups
-  // per CU) measured faster than double-buffered on every Mask R-CNN shape,
-  // f32 and split, large grids and small.
-  const bool db = false;
-  // r5: the streaming short-K 1x1 kernel (conv1x1_stream_kernel) for the
-  // memory-bound stride-1 1x1s, when the plan has no split-K
-  {
-    const int sk = stream1x1_variant(a, p, flags);
-    if (sk > 0) return launch_stream1x1(sk, a, stream);
+  if (p.family == kConvStream1x1) {
+    launch_stream1x1(p, st, a);
+    D2MI_LAUNCH_CHECK();
+    return 0;
   }
   // Split-K partials go to the workspace and a second launch sums them in a
   // fixed order + applies the epilogue (deterministic).  r3 measured the
@@ -1846,36 +1689,33 @@ static int conv_core(const float* x, const float* w_packed, const float* bias,
   // tile, agent-scope release / acquire): bit-identical but 6 % slower in the
   // step -- one workgroup reads its tile's 64-128 KiB slabs at ~100 GB/s --
   // and r4 removed it.
-  auto launch = [&](const ConvArgs& c) {
-    const dim3 g(c.ntiles, c.splits);
-    if (flags & kSplit3)
-      launch_conv<true>(p.cfg, db, g, st, c);
+  auto launch = [&](const ConvLaunch& l, float* slab) {
+    if (l.tiles == 0) return 0;
+    ConvArgs c = a;
+    c.tile_base = l.tile0;
+    c.ntiles = l.tiles;
+    c.m_base = l.m_base;
+    c.m_end = l.m_end;
+    c.splits = l.splits;
+    c.kt_per_split = l.kt_per_split;
+    c.partial = l.splits > 1 ? slab : nullptr;
+    const dim3 g(l.tiles, l.splits);
+    if (p.split3)
+      launch_conv<true, false>(p.family, p.occ, g, st, c);
     else
-      launch_conv<false>(p.cfg, db, g, st, c);
+      launch_conv<false, false>(p.family, p.occ, g, st, c);
     D2MI_LAUNCH_CHECK();
-    if (c.splits > 1) {
-      const int64_t total = (int64_t)(c.m_end - c.m_base) * Cout;
-      // (the float4 epilogue reads bias / top-down / residual / gate as float4s)
-      const uintptr_t ops4 = (uintptr_t)c.bias | (uintptr_t)c.topdown | (uintptr_t)c.residual |
-                             (uintptr_t)c.gate;
-      if (Cout % 4 == 0 && ((uintptr_t)c.partial & 15) == 0 && ((uintptr_t)y & 15) == 0 &&
-          (ops4 & 15) == 0) {
-        const int gr = (int)std::min<int64_t>((total / 4 + 255) / 256, 8192);
-        hipLaunchKernelGGL(splitk_reduce4_kernel, dim3(gr), dim3(256), 0, st, c);
-      } else {
-        const int gr = (int)std::min<int64_t>((total + 255) / 256, 4096);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(gr), dim3(256), 0, st, c);
-      }
-      D2MI_LAUNCH_CHECK();
-    }
+    if (l.reduce == kReduceNone) return 0;
+    // (the float4 form reads bias / top-down / residual / gate as float4s)
+    if (l.reduce == kReduceFloat4)
+      hipLaunchKernelGGL(splitk_reduce4_kernel, dim3(l.reduce_grid), dim3(256), 0, st, c);
+    else
+      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(l.reduce_grid), dim3(256), 0, st, c);
+    D2MI_LAUNCH_CHECK();
     return 0;
   };
-  if (a.ntiles > 0) {
-    const int rc = launch(a);
-    if (rc) return rc;
-  }
-  if (p.tail_tiles > 0) return launch(t);
-  return 0;
+  if (const int rc = launch(p.main, sp.main)) return rc;
+  return launch(p.tail, sp.tail);
 }
 
 
@@ -1885,20 +1725,14 @@ static int conv_f32(const float* x, const float* w_packed, const float* bias,
                     int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
                     int pad_beg, int pad_end, int flags, void* workspace, size_t workspace_bytes,
                     void* stream) {
-  D2MI_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0,
-               "bad conv shape");
-  D2MI_REQUIRE(Cin % 4 == 0, "Cin must be a multiple of 4 (got %d)", Cin);
+  if (conv_check_shape(N, H, W, Cin, Cout, KH, KW, stride)) return -1;
   D2MI_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w_packed & 15) == 0,
                "x and w must be 16-byte aligned");
-  const int64_t img_bytes = (int64_t)H * W * Cin * sizeof(float);
-  D2MI_REQUIRE(img_bytes < (1ll << 31), "one conv input image must be < 2 GiB");
-  D2MI_REQUIRE((int64_t)KH * KW * Cin * Cout * sizeof(float) < (1ll << 31),
-               "conv weights must be < 2 GiB");
-  if ((int64_t)N * img_bytes >= (1ll << 31)) {
+  const int chunk = conv_chunk(N, H, W, Cin);
+  if (chunk < N) {
     int OH0, OW0;
     D2MI_REQUIRE(conv_dims(H, W, KH, KW, stride, pad_beg, pad_end, OH0, OW0) == 0,
                  "conv output is empty");
-    const int chunk = (int)(((1ll << 31) - 1) / img_bytes);
     const size_t xs = (size_t)H * W * Cin, ys = (size_t)OH0 * OW0 * Cout;
     const size_t ts = (size_t)((OH0 + 1) / 2) * ((OW0 + 1) / 2) * Cout;
     for (int n0 = 0; n0 < N; n0 += chunk) {
@@ -1955,39 +1789,56 @@ extern "C" int d2mi_conv2d_nhwc(const float* x, const float* w_packed, const flo
                              stride, pad_beg, pad_end, act ? kRelu : 0, nullptr, 0, stream);
 }
 
-// Split-K plan of a multi-level launch: the single-level rule on the total
-// tile count (Cout % 4 == 0 for the level-aware reduce).
-static int levels_splits(const int32_t* dims, int nlev, int Cin, int Cout, int KH, int KW,
-                         int stride, int pad_beg, int pad_end, int64_t* rows, int* ntiles) {
-  const Plan p0 = make_plan(1, Cout, KH, KW, Cin, Cout % 4 == 0, false);  // (no cfg 3)
-  const int nN = (Cout + p0.BN - 1) / p0.BN;
-  int64_t r = 0;
-  int t = 0;
+// What d2mi_conv2d_nhwc_levels and d2mi_conv2d_levels_plan refuse of the shape.
+static int levels_check_shape(const int32_t* dims, int nlev, int Cin, int Cout, int KH, int KW,
+                              int stride, int pad_beg, int pad_end, int flags) {
+  D2MI_REQUIRE(nlev >= 1 && nlev <= kMaxConvLevels, "nlev=%d out of [1,%d]", nlev, kMaxConvLevels);
+  D2MI_REQUIRE(Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0, "bad conv shape");
+  D2MI_REQUIRE(Cin % 4 == 0, "Cin must be a multiple of 4 (got %d)", Cin);
+  D2MI_REQUIRE((flags & ~(kRelu | kSplit3)) == 0,
+               "multi-level conv flags: bit0 relu, bit2 split-bf16 MFMA products");
+  D2MI_REQUIRE((int64_t)KH * KW * Cin * Cout * sizeof(float) < (1ll << 31),
+               "conv weights must be < 2 GiB");
   for (int l = 0; l < nlev; ++l) {
-    int OH = 0, OW = 0;
-    conv_dims(dims[3 * l + 1], dims[3 * l + 2], KH, KW, stride, pad_beg, pad_end, OH, OW);
-    const int64_t M = (int64_t)dims[3 * l] * OH * OW;
-    r += M;
-    t += (int)((M + p0.BM - 1) / p0.BM) * nN;
+    const int N = dims[3 * l], H = dims[3 * l + 1], W = dims[3 * l + 2];
+    int OH, OW;
+    D2MI_REQUIRE(N > 0 && H > 0 && W > 0 &&
+                     conv_dims(H, W, KH, KW, stride, pad_beg, pad_end, OH, OW) == 0,
+                 "level %d: bad or empty conv geometry", l);
+    D2MI_REQUIRE((int64_t)N * H * W * Cin * 4 < (1ll << 31), "level %d input must be < 2 GiB", l);
   }
-  *rows = r;
-  *ntiles = t;
-  const int G = wg_slots(p0.cfg);
-  const int nk = KH * KW * ((Cin + BK - 1) / BK);
-  if (Cout % 4 || !(4 * t < 3 * G && nk >= 16)) return 1;
-  const int S = std::min(std::max(1, G / std::max(t, 1)), std::min(nk / 8, 16));
-  const int kps = (nk + S - 1) / S;
-  return (nk + kps - 1) / kps;
+  return 0;
 }
 
 extern "C" size_t d2mi_conv2d_levels_workspace_size(const int32_t* dims, int nlev, int Cin,
                                                     int Cout, int KH, int KW, int stride,
                                                     int pad_beg, int pad_end) {
   if (nlev < 1 || nlev > kMaxConvLevels) return 0;
-  int64_t rows;
-  int t;
-  const int S = levels_splits(dims, nlev, Cin, Cout, KH, KW, stride, pad_beg, pad_end, &rows, &t);
-  return S > 1 ? (size_t)S * rows * Cout * sizeof(float) : 0;
+  ConvLevelsPlan p;
+  plan_conv_levels(dims, nlev, Cin, Cout, KH, KW, stride, pad_beg, pad_end,
+                   kOpAllAligned | kOpWorkspace, SIZE_MAX, device_cus(), &p);
+  return p.ws_bytes;
+}
+
+extern "C" int d2mi_conv2d_levels_plan(const int32_t* dims, int nlev, int Cin, int Cout, int KH,
+                                       int KW, int stride, int pad_beg, int pad_end, int flags,
+                                       int operands, size_t workspace_bytes, int32_t* out,
+                                       int out_len) {
+  D2MI_REQUIRE(dims != nullptr && (operands & ~127) == 0, "levels plan: bad arguments");
+  if (levels_check_shape(dims, nlev, Cin, Cout, KH, KW, stride, pad_beg, pad_end, flags)) return -1;
+  ConvLevelsPlan p;
+  plan_conv_levels(dims, nlev, Cin, Cout, KH, KW, stride, pad_beg, pad_end, operands,
+                   workspace_bytes, device_cus(), &p);
+  int32_t v[15 + 2 * (kMaxConvLevels + 1)];
+  int n = 0;
+  for (int f : {p.family, p.occ, (int)((flags & kSplit3) != 0), p.lds_epi, p.BM, p.BN, p.nN, p.nk,
+                p.ntiles, p.splits, p.kt_per_split, p.reduce_grid, nlev})
+    v[n++] = f;
+  for (int l = 0; l <= kMaxConvLevels; ++l) v[n++] = p.tile0[l];
+  for (int l = 0; l <= kMaxConvLevels; ++l) v[n++] = p.moff[l];
+  v[n++] = (int32_t)(p.ws_bytes & 0x7fffffff);
+  v[n++] = (int32_t)(p.ws_bytes >> 31);
+  return emit_plan(v, n, out, out_len);
 }
 
 extern "C" int d2mi_conv2d_nhwc_levels(const float* const* xs, const int32_t* dims, int nlev,
@@ -1995,14 +1846,20 @@ extern "C" int d2mi_conv2d_nhwc_levels(const float* const* xs, const int32_t* di
                                        int Cin, int Cout, int KH, int KW, int stride, int pad_beg,
                                        int pad_end, int flags, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-  D2MI_REQUIRE(nlev >= 1 && nlev <= kMaxConvLevels, "nlev=%d out of [1,%d]", nlev, kMaxConvLevels);
-  D2MI_REQUIRE(Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0, "bad conv shape");
-  D2MI_REQUIRE(Cin % 4 == 0, "Cin must be a multiple of 4 (got %d)", Cin);
-  D2MI_REQUIRE((flags & ~(kRelu | kSplit3)) == 0,
-               "multi-level conv flags: bit0 relu, bit2 split-bf16 MFMA products");
+  if (levels_check_shape(dims, nlev, Cin, Cout, KH, KW, stride, pad_beg, pad_end, flags)) return -1;
   D2MI_REQUIRE(((uintptr_t)w_packed & 15) == 0, "w must be 16-byte aligned");
-  D2MI_REQUIRE((int64_t)KH * KW * Cin * Cout * sizeof(float) < (1ll << 31),
-               "conv weights must be < 2 GiB");
+  uintptr_t yor = 0;
+  for (int l = 0; l < nlev; ++l) {
+    D2MI_REQUIRE(((uintptr_t)xs[l] & 15) == 0, "level %d input must be 16-byte aligned", l);
+    yor |= (uintptr_t)ys[l];
+  }
+  ConvLevelsPlan p;
+  plan_conv_levels(dims, nlev, Cin, Cout, KH, KW, stride, pad_beg, pad_end,
+                   plan_operands(nullptr, nullptr, nullptr, (const void*)yor, nullptr, workspace),
+                   workspace_bytes, device_cus(), &p);
+  ConvLevelsSpace sp;
+  Workspace carve(workspace, workspace_bytes);
+  sp.lay(carve, p.splits, p.moff[kMaxConvLevels], Cout);
   ConvArgs a = {};
   a.w = w_packed;
   a.w_bytes = (int)((int64_t)KH * KW * Cin * Cout * 4);
@@ -2015,61 +1872,30 @@ extern "C" int d2mi_conv2d_nhwc_levels(const float* const* xs, const int32_t* di
   a.pad = pad_beg;
   a.flags = flags;
   a.nlev = nlev;
-  bool al = (Cout % 4) == 0;
-  int64_t Mtot = 0;
   for (int l = 0; l < nlev; ++l) {
-    const int N = dims[3 * l], H = dims[3 * l + 1], W = dims[3 * l + 2];
-    int OH, OW;
-    D2MI_REQUIRE(N > 0 && H > 0 && W > 0 &&
-                     conv_dims(H, W, KH, KW, stride, pad_beg, pad_end, OH, OW) == 0,
-                 "level %d: bad or empty conv geometry", l);
-    D2MI_REQUIRE((int64_t)N * H * W * Cin * 4 < (1ll << 31), "level %d input must be < 2 GiB", l);
-    D2MI_REQUIRE(((uintptr_t)xs[l] & 15) == 0, "level %d input must be 16-byte aligned", l);
-    al = al && ((uintptr_t)ys[l] & 15) == 0;
     a.lv_x[l] = xs[l];
     a.lv_y[l] = ys[l];
     a.lv_gate[l] = nullptr;
-    a.lv_N[l] = N;
-    a.lv_H[l] = H;
-    a.lv_W[l] = W;
-    a.lv_OH[l] = OH;
-    a.lv_OW[l] = OW;
-    a.lv_xbytes[l] = (int)((int64_t)N * H * W * Cin * 4);
-    Mtot += (int64_t)N * OH * OW;
+    a.lv_N[l] = dims[3 * l];
+    a.lv_H[l] = dims[3 * l + 1];
+    a.lv_W[l] = dims[3 * l + 2];
+    a.lv_OH[l] = p.OH[l];
+    a.lv_OW[l] = p.OW[l];
+    a.lv_xbytes[l] = (int)((int64_t)a.lv_N[l] * a.lv_H[l] * a.lv_W[l] * Cin * 4);
   }
-  a.lds_epi = al;
-  // multi-level launches keep the 128-row kernels (no cfg 3: r3 measured the
-  // multi-level warp-specialised form neutral for Mask R-CNN and 2-8 %
-  // slower for the RetinaNet / SOLOv2 towers; removed in r4)
+  for (int l = 0; l <= kMaxConvLevels; ++l) {
+    a.lv_tile0[l] = p.tile0[l];
+    a.lv_moff[l] = p.moff[l];
+  }
+  a.lds_epi = p.lds_epi;
   a.reg_partials = 0;
-  const Plan p = make_plan((int)std::min<int64_t>(Mtot, 1 << 30), Cout, KH, KW, Cin, al, false);
-  a.nN = (Cout + p.BN - 1) / p.BN;
-  int t = 0;
-  for (int l = 0; l < nlev; ++l) {
-    a.lv_tile0[l] = t;
-    t += (a.lv_N[l] * a.lv_OH[l] * a.lv_OW[l] + p.BM - 1) / p.BM * a.nN;
-  }
-  a.lv_tile0[nlev] = t;
-  a.ntiles = t;
+  a.nN = p.nN;
+  a.ntiles = p.ntiles;
   a.tile_base = 0;
-  a.nk = KH * KW * ((Cin + BK - 1) / BK);
-  {
-    int64_t rows;
-    int tt;
-    int S = levels_splits(dims, nlev, Cin, Cout, KH, KW, stride, pad_beg, pad_end, &rows, &tt);
-    if (S > 1 && (workspace == nullptr || workspace_bytes < (size_t)S * rows * Cout * 4 ||
-                  ((uintptr_t)workspace & 15) != 0 || !al))
-      S = 1;  // no (usable) workspace: one pass per tile
-    a.splits = S;
-    a.kt_per_split = (a.nk + S - 1) / S;
-    a.partial = S > 1 ? (float*)workspace : nullptr;
-    int64_t off = 0;
-    for (int l = 0; l <= kMaxConvLevels; ++l) {
-      a.lv_moff[l] = (int)off;
-      if (l < nlev) off += (int64_t)a.lv_N[l] * a.lv_OH[l] * a.lv_OW[l];
-    }
-    for (int l = nlev; l <= kMaxConvLevels; ++l) a.lv_moff[l] = (int)rows;
-  }
+  a.nk = p.nk;
+  a.splits = p.splits;
+  a.kt_per_split = p.kt_per_split;
+  a.partial = sp.partial;
   a.cchunks = (Cin + BK - 1) / BK;
   // level 0's geometry in the single-level fields (unused by the kernel)
   a.x = xs[0];
@@ -2083,16 +1909,15 @@ extern "C" int d2mi_conv2d_nhwc_levels(const float* const* xs, const int32_t* di
   a.m_end = a.M;
   a.x_bytes = a.lv_xbytes[0];
   a.tdH = a.tdW = 1;
-  const dim3 grid(a.ntiles, a.splits);
+  const dim3 grid(p.ntiles, p.splits);
   if (flags & kSplit3)
-    launch_conv_levels<true>(p.cfg, grid, as_stream(stream), a);
+    launch_conv<true, true>(p.family, p.occ, grid, as_stream(stream), a);
   else
-    launch_conv_levels<false>(p.cfg, grid, as_stream(stream), a);
+    launch_conv<false, true>(p.family, p.occ, grid, as_stream(stream), a);
   D2MI_LAUNCH_CHECK();
-  if (a.splits > 1) {
-    const int64_t total = (int64_t)a.lv_moff[kMaxConvLevels] * (Cout / 4);
-    const int gr = (int)std::min<int64_t>((total + 255) / 256, 8192);
-    hipLaunchKernelGGL(splitk_reduce_levels_kernel, dim3(gr), dim3(256), 0, as_stream(stream), a);
+  if (p.splits > 1) {
+    hipLaunchKernelGGL(splitk_reduce_levels_kernel, dim3(p.reduce_grid), dim3(256), 0,
+                       as_stream(stream), a);
     D2MI_LAUNCH_CHECK();
   }
   return 0;

@@ -18,6 +18,7 @@
 // FIXED split order (deterministic).  Global loads of the next chunk are issued
 // before the current chunk's MFMAs (register double buffering).
 #include "common.h"
+#include "conv_plan.h"
 #include "internal.h"
 
 namespace d2mi {
@@ -25,7 +26,7 @@ namespace {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
-constexpr int KP = 32;  // pixels per k-step
+constexpr int KP = kWgradKP;  // pixels per k-step
 
 struct WgradArgs {
   const float* x;   // [N,H,W,Cin]
@@ -42,7 +43,7 @@ struct WgradArgs {
   // the reduce then adds the sum into dw / dbias)
   int part;
   int x_bytes, dy_bytes;  // buffer ranges (split kernel; < 2 GiB)
-  // D2MI_WGRAD_PRIO (default 1, 0 off): wave priority 1 while issuing the
+  // tuning "wgrad_prio" (default 1, 0 off): wave priority 1 while issuing the
   // chunk's MFMAs, as conv_mfma.hip.  Measured (tools/ab_prio.sh): the wgrad
   // set 1.9 % faster in total (FPN p2 3x3 1025 -> 1008 us, res5 3x3 97 -> 92),
   // the training bench +1.4 % (89.6 -> 90.9 img/s, two alternating pairs).
@@ -737,81 +738,6 @@ FastDiv make_fastdiv(uint32_t d) {
   return f;
 }
 
-struct WPlan {
-  int TM, TN, BM, BN, ntiles, splits, chunks_per_split, nchunks;
-  bool occ3;
-  bool ws;  // conv_wgrad_ws_kernel (256 x 128 tiles, one workgroup per CU)
-};
-
-// The 128x128 split wgrad can run three workgroups per CU (168 VGPRs, 52 KiB
-// LDS).  Measured (tools/conv_ab.py --set wgrad): 3% faster on the FPN p2 3x3
-// (134,400 pixels), slower on everything smaller (the extra pixel splits cost
-// more partial traffic than the occupancy gains), so only pixel counts of
-// 64k and up take it.  D2MI_WGRAD_OCC=2 disables it (A/B).
-static bool wgrad_occ3() {
-  static const int on = [] {
-    const char* e = getenv("D2MI_WGRAD_OCC");
-    return !(e && e[0] == '2');
-  }();
-  return on;
-}
-
-// split3: the split-product math (the warp-specialised kernel exists only in
-// that form).  It takes the KxK convs with Cin % 256 == 0, Cout % 128 == 0
-// (tuning "wgrad_ws"; tools/ws_ab.py --key wgrad_ws: 3x3 shapes 10-20 %
-// faster, the 1x1s 9 % slower -- their 8 chunks of 32 pixels per split are
-// too short for its prologue).
-WPlan wplan(int N, int OH, int OW, int Cin, int Cout, int KH, int KW, bool split3 = true) {
-  WPlan p;
-  // 128 x 128 tiles for 256-wide channels; 64-wide when a dimension is small
-  p.TM = Cin > 64 ? 2 : 1;
-  p.TN = Cout > 64 ? 2 : 1;
-  // 1x1s (tuning "wgrad_ws1"): only from ~6 GFLOP up -- the smaller ones have
-  // too few 256x128 tiles x 16-chunk splits to fill the chip (tools/wgrad_ws1_ab.sh:
-  // the FPN p2 lateral 165 -> 140 us, the strided shortcuts 8-13 % faster,
-  // the 4.4 GFLOP res4 1x1s 7 % slower)
-  // (tuning value = the GFLOP threshold; 0 = off)
-  const bool ws1 = KH * KW == 1 && tuning(kTuneWgradWS1) > 0 &&
-                   2.0 * N * OH * OW * (double)Cin * Cout >= tuning(kTuneWgradWS1) * 1e9;
-  p.ws = split3 && tuning(kTuneWgradWS) > 0 && (KH * KW > 1 || ws1) && Cin % 256 == 0 &&
-         Cout % 128 == 0;
-  p.BM = p.ws ? 256 : 64 * p.TM;
-  p.BN = 64 * p.TN;
-  p.ntiles = KH * KW * ((Cin + p.BM - 1) / p.BM) * ((Cout + p.BN - 1) / p.BN);
-  const long long P = (long long)N * OH * OW;
-  p.nchunks = (int)((P + KP - 1) / KP);
-  // about one round of resident workgroups (2 or 3 per CU), each walking
-  // >= 16 chunks
-  // D2MI_WGRAD_OCC3_MIN_P: the pixel count from which the 3-per-CU kernel runs (A/B)
-  static const long long occ3_min_p = [] {
-    const char* e = getenv("D2MI_WGRAD_OCC3_MIN_P");
-    return e ? atoll(e) : 65536LL;
-  }();
-  p.occ3 = !p.ws && p.TM == 2 && p.TN == 2 && P >= occ3_min_p && wgrad_occ3();
-  // D2MI_WGRAD_SLOTS / D2MI_WGRAD_MINCH: the split target and the minimum
-  // chunks per split (A/B knobs)
-  static const int slots_env = [] {
-    const char* e = getenv("D2MI_WGRAD_SLOTS");
-    return e ? atoi(e) : 0;
-  }();
-  static const int minch = [] {
-    const char* e = getenv("D2MI_WGRAD_MINCH");
-    return e && atoi(e) > 0 ? atoi(e) : 16;
-  }();
-  const int G = slots_env > 0 ? slots_env : (p.ws ? 256 : (p.occ3 ? 768 : 512));
-  int splits = std::max(1, G / p.ntiles);
-  splits = std::min(splits, std::max(1, p.nchunks / minch));
-  // D2MI_WGRAD_MAXSPLIT: the cap on splits (A/B knob)
-  static const int maxsplit = [] {
-    const char* e = getenv("D2MI_WGRAD_MAXSPLIT");
-    return e && atoi(e) > 0 ? atoi(e) : 128;
-  }();
-  splits = std::min(splits, maxsplit);
-  p.chunks_per_split = (p.nchunks + splits - 1) / splits;
-  p.splits = (p.nchunks + p.chunks_per_split - 1) / p.chunks_per_split;
-  return p;
-}
-
 }  // namespace
 }  // namespace d2mi
 
@@ -821,33 +747,76 @@ extern "C" size_t d2mi_conv2d_wgrad_workspace_size(int N, int H, int W, int Cin,
                                                    int KW, int stride, int pad_beg, int pad_end) {
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0)
     return 0;
-  const int OH = (H + pad_beg + pad_end - KH) / stride + 1;
-  const int OW = (W + pad_beg + pad_end - KW) / stride + 1;
-  if (OH <= 0 || OW <= 0) return 0;
   // the larger of the split-product and the f32 plans (either math mode fits)
-  const int s = std::max(wplan(N, OH, OW, Cin, Cout, KH, KW, true).splits,
-                         wplan(N, OH, OW, Cin, Cout, KH, KW, false).splits);
-  return s > 1 ? (size_t)s * ((size_t)KH * KW * Cin * Cout + Cout) * sizeof(float) : 0;
+  const ConvShape s = {N, H, W, Cin, Cout, KH, KW, stride, pad_beg, pad_end};
+  WgradPlan split, f32;
+  if (plan_wgrad(s, kPlanSplit3, kOpAllAligned | kOpWorkspace, SIZE_MAX, &split) ||
+      plan_wgrad(s, 0, kOpAllAligned | kOpWorkspace, SIZE_MAX, &f32))
+    return 0;
+  return std::max(split.ws_bytes, f32.ws_bytes);
+}
+
+// The checks of d2mi_conv2d_wgrad_ex that need no pointer, then its plan.
+static int wgrad_plan_checked(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                              int pad_beg, int pad_end, int flags, int operands,
+                              size_t workspace_bytes, WgradPlan* p) {
+  D2MI_REQUIRE((flags & ~12) == 0,
+               "wgrad flags: bit2 = split-bf16 products, bit3 = accumulate into dw / dbias");
+  D2MI_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0,
+               "bad conv shape");
+  D2MI_REQUIRE(Cin % 4 == 0 && Cout % 4 == 0, "Cin and Cout must be multiples of 4 (%d, %d)",
+               Cin, Cout);
+  int OH, OW;
+  D2MI_REQUIRE(conv_dims(H, W, KH, KW, stride, pad_beg, pad_end, OH, OW) == 0,
+               "conv output is empty");
+  D2MI_REQUIRE((long long)N * OH * OW < (1LL << 31), "too many pixels");
+  if (flags & kPlanSplit3)
+    D2MI_REQUIRE((int64_t)N * H * W * Cin * 4 < (1ll << 31) &&
+                     (int64_t)N * OH * OW * Cout * 4 < (1ll << 31),
+                 "split wgrad: x and dy must each be < 2 GiB");
+  plan_wgrad({N, H, W, Cin, Cout, KH, KW, stride, pad_beg, pad_end}, flags, operands,
+             workspace_bytes, p);
+  if (flags & kPlanAccum)  // the sum goes through the reduce, which adds it: one slab at least
+    D2MI_REQUIRE((operands & kOpWorkspace) && workspace_bytes >= p->ws_bytes,
+                 "accumulating wgrad: workspace must hold %d slab(s)", p->splits);
+  return 0;
+}
+
+// The plan as integers (include/d2mi.h lists the fields).
+extern "C" int d2mi_conv2d_wgrad_plan(int N, int H, int W, int Cin, int Cout, int KH, int KW,
+                                      int stride, int pad_beg, int pad_end, int flags,
+                                      int operands, size_t workspace_bytes, int32_t* out,
+                                      int out_len) {
+  D2MI_REQUIRE((operands & ~127) == 0, "wgrad plan: unknown operand bits");
+  WgradPlan p;
+  if (wgrad_plan_checked(N, H, W, Cin, Cout, KH, KW, stride, pad_beg, pad_end, flags, operands,
+                         workspace_bytes, &p))
+    return -1;
+  const int32_t v[] = {p.kernel, p.TM, p.TN, p.BM, p.BN, p.nCi, p.nCo, p.ntiles, p.nchunks,
+                       p.splits, p.chunks_per_split, p.part, p.reduce, p.reduce_grid,
+                       (int32_t)(p.ws_bytes & 0x7fffffff), (int32_t)(p.ws_bytes >> 31)};
+  return emit_plan(v, (int)(sizeof(v) / sizeof(v[0])), out, out_len);
 }
 
 extern "C" int d2mi_conv2d_wgrad_ex(const float* x, const float* dy, float* dw_hwio,
                                     float* dbias, int N, int H, int W, int Cin, int Cout, int KH,
                                     int KW, int stride, int pad_beg, int pad_end, int flags,
                                     void* workspace, size_t workspace_bytes, void* stream) {
-  D2MI_REQUIRE((flags & ~12) == 0,
-               "wgrad flags: bit2 = split-bf16 products, bit3 = accumulate into dw / dbias");
-  const bool accum = (flags & 8) != 0;
-  D2MI_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0,
-               "bad conv shape");
-  D2MI_REQUIRE(Cin % 4 == 0 && Cout % 4 == 0, "Cin and Cout must be multiples of 4 (%d, %d)",
-               Cin, Cout);
-  D2MI_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0,
-               "x and dy must be 16-byte aligned");
-  WgradArgs a = {};
-  {
-    static const char* e = getenv("D2MI_WGRAD_PRIO");
-    a.prio = e ? atoi(e) : 1;
+  auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+  WgradPlan p;
+  if (wgrad_plan_checked(N, H, W, Cin, Cout, KH, KW, stride, pad_beg, pad_end, flags,
+                         (al16(dw_hwio) ? kOpAligned : 0) | (workspace ? kOpWorkspace : 0) |
+                             (al16(workspace) ? kOpWsAligned : 0),
+                         workspace_bytes, &p))
+    return -1;
+  D2MI_REQUIRE(al16(x) && al16(dy), "x and dy must be 16-byte aligned");
+  WgradSpace sp = {};
+  if (p.part) {
+    Workspace carve(workspace, workspace_bytes);
+    sp.lay(carve, p.splits, (size_t)KH * KW * Cin * Cout, Cout);
   }
+  WgradArgs a = {};
+  a.prio = tuning(kTuneWgradPrio);
   a.xcd = tuning(kTuneWgradXCD) > 0 ? 1 : 0;
   a.x = x;
   a.dy = dy;
@@ -862,92 +831,65 @@ extern "C" int d2mi_conv2d_wgrad_ex(const float* x, const float* dy, float* dw_h
   a.KW = KW;
   a.stride = stride;
   a.pad = pad_beg;
-  a.OH = (H + pad_beg + pad_end - KH) / stride + 1;
-  a.OW = (W + pad_beg + pad_end - KW) / stride + 1;
-  D2MI_REQUIRE(a.OH > 0 && a.OW > 0, "conv output is empty");
-  D2MI_REQUIRE((long long)N * a.OH * a.OW < (1LL << 31), "too many pixels");
+  a.OH = p.OH;
+  a.OW = p.OW;
   a.P = N * a.OH * a.OW;
-  const bool split3 = (flags & 4) != 0;
-  WPlan p = wplan(N, a.OH, a.OW, Cin, Cout, KH, KW, split3);
-  const size_t need =
-      p.splits > 1 ? (size_t)p.splits * ((size_t)KH * KW * Cin * Cout + Cout) * sizeof(float) : 0;
-  if (need > workspace_bytes || workspace == nullptr) {  // no workspace: one split
-    p.splits = 1;
-    p.chunks_per_split = p.nchunks;
-  }
-  if (accum)  // the sum goes through the reduce, which adds it: one slab at least
-    D2MI_REQUIRE(workspace != nullptr &&
-                     workspace_bytes >= (size_t)p.splits *
-                                            ((size_t)KH * KW * Cin * Cout + Cout) * sizeof(float),
-                 "accumulating wgrad: workspace must hold %d slab(s)", p.splits);
-  a.nCi = (Cin + p.BM - 1) / p.BM;
-  a.nCo = (Cout + p.BN - 1) / p.BN;
+  a.nCi = p.nCi;
+  a.nCo = p.nCo;
   a.ntiles = p.ntiles;
   a.splits = p.splits;
   a.chunks_per_split = p.chunks_per_split;
   a.nchunks = p.nchunks;
-  a.part = p.splits > 1 || accum;
-  a.partial = a.part ? (float*)workspace : nullptr;
-  a.pbias = a.part ? (float*)workspace + (size_t)p.splits * KH * KW * Cin * Cout : nullptr;
+  a.part = p.part;
+  a.partial = sp.dw;
+  a.pbias = sp.dbias;
   hipStream_t st = as_stream(stream);
-  dim3 grid(a.ntiles, a.splits);
-  if (split3) {
-    D2MI_REQUIRE((int64_t)N * H * W * Cin * 4 < (1ll << 31) &&
-                     (int64_t)a.P * Cout * 4 < (1ll << 31),
-                 "split wgrad: x and dy must each be < 2 GiB");
+  const dim3 grid(p.ntiles, p.splits);
+  if (p.kernel != kWgradF32) {
     a.x_bytes = (int)((int64_t)N * H * W * Cin * 4);
     a.dy_bytes = (int)((int64_t)a.P * Cout * 4);
-    const FastDiv fhw = make_fastdiv((uint32_t)(a.OH * a.OW)), fw = make_fastdiv((uint32_t)a.OW);
-    // tuning wgrad_ws: 1 = loads one chunk ahead (no spills), 2 = two chunks
-    // ahead (10 VGPRs of the stagers' ring spill at the 128-VGPR budget)
-    // the incremental pixel cursor (conv_wgrad_ws_kernel INC): same-size
-    // stride-1 convs whose per-thread runs of 4 pixels and 32-pixel chunk
-    // steps wrap at most one row and one image, pixel indices < 2^24
-    const bool inc = a.stride == 1 && a.OH == H && a.OW == W && a.OW >= 4 &&
-                     KP / a.OW + 1 <= a.OH && (int64_t)a.P + KP < (1 << 24) &&
-                     tuning(kTuneWgradInc) > 0;
-    if (p.ws && tuning(kTuneWgradWS) >= 2)
-      hipLaunchKernelGGL((conv_wgrad_ws_kernel<2>), grid, dim3(1024), 0, st, a, fhw, fw);
-    else if (p.ws && inc)
-      hipLaunchKernelGGL((conv_wgrad_ws_kernel<1, true>), grid, dim3(1024), 0, st, a, fhw, fw);
-    else if (p.ws)
-      hipLaunchKernelGGL((conv_wgrad_ws_kernel<1>), grid, dim3(1024), 0, st, a, fhw, fw);
-    else if (p.occ3)
-      hipLaunchKernelGGL((conv_wgrad_split_kernel<2, 2, 3>), grid, dim3(256), 0, st, a, fhw, fw);
-    else if (p.TM == 2 && p.TN == 2)
-      hipLaunchKernelGGL((conv_wgrad_split_kernel<2, 2>), grid, dim3(256), 0, st, a, fhw, fw);
-    else if (p.TM == 2)
-      hipLaunchKernelGGL((conv_wgrad_split_kernel<2, 1>), grid, dim3(256), 0, st, a, fhw, fw);
-    else if (p.TN == 2)
-      hipLaunchKernelGGL((conv_wgrad_split_kernel<1, 2>), grid, dim3(256), 0, st, a, fhw, fw);
-    else
-      hipLaunchKernelGGL((conv_wgrad_split_kernel<1, 1>), grid, dim3(256), 0, st, a, fhw, fw);
-  } else if (p.TM == 2 && p.TN == 2)
+  }
+  const FastDiv fhw = make_fastdiv((uint32_t)(a.OH * a.OW)), fw = make_fastdiv((uint32_t)a.OW);
+  const int tm = p.TM, tn = p.TN;
+  if (p.kernel == kWgradWS2)
+    hipLaunchKernelGGL((conv_wgrad_ws_kernel<2>), grid, dim3(1024), 0, st, a, fhw, fw);
+  else if (p.kernel == kWgradWSInc)
+    hipLaunchKernelGGL((conv_wgrad_ws_kernel<1, true>), grid, dim3(1024), 0, st, a, fhw, fw);
+  else if (p.kernel == kWgradWS)
+    hipLaunchKernelGGL((conv_wgrad_ws_kernel<1>), grid, dim3(1024), 0, st, a, fhw, fw);
+  else if (p.kernel == kWgradSplitOcc3)
+    hipLaunchKernelGGL((conv_wgrad_split_kernel<2, 2, 3>), grid, dim3(256), 0, st, a, fhw, fw);
+  else if (p.kernel == kWgradSplit && tm == 2 && tn == 2)
+    hipLaunchKernelGGL((conv_wgrad_split_kernel<2, 2>), grid, dim3(256), 0, st, a, fhw, fw);
+  else if (p.kernel == kWgradSplit && tm == 2)
+    hipLaunchKernelGGL((conv_wgrad_split_kernel<2, 1>), grid, dim3(256), 0, st, a, fhw, fw);
+  else if (p.kernel == kWgradSplit && tn == 2)
+    hipLaunchKernelGGL((conv_wgrad_split_kernel<1, 2>), grid, dim3(256), 0, st, a, fhw, fw);
+  else if (p.kernel == kWgradSplit)
+    hipLaunchKernelGGL((conv_wgrad_split_kernel<1, 1>), grid, dim3(256), 0, st, a, fhw, fw);
+  else if (tm == 2 && tn == 2)
     hipLaunchKernelGGL((conv_wgrad_kernel<2, 2>), grid, dim3(256), 0, st, a);
-  else if (p.TM == 2)
+  else if (tm == 2)
     hipLaunchKernelGGL((conv_wgrad_kernel<2, 1>), grid, dim3(256), 0, st, a);
-  else if (p.TN == 2)
+  else if (tn == 2)
     hipLaunchKernelGGL((conv_wgrad_kernel<1, 2>), grid, dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL((conv_wgrad_kernel<1, 1>), grid, dim3(256), 0, st, a);
   D2MI_LAUNCH_CHECK();
-  if (a.part) {
-    const size_t total = (size_t)KH * KW * Cin * Cout;
-    if (total % 4 == 0 && ((uintptr_t)a.partial & 15) == 0 && ((uintptr_t)dw_hwio & 15) == 0) {
-      const size_t total4 = total / 4;
-      const int g4 = (int)std::min<size_t>((total4 + Cout + 255) / 256, 8192);
-      hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3(g4), dim3(256), 0, st,
-                         reinterpret_cast<const float4*>(a.partial), a.splits, total4,
-                         reinterpret_cast<float4*>(dw_hwio), a.pbias, Cout, dbias, (int)accum);
-    } else {
-      const int g = (int)std::min<size_t>((total + Cout + 255) / 256, 4096);
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(g), dim3(256), 0, st, a.partial, a.splits,
-                         total, dw_hwio, a.pbias, Cout, dbias, (int)accum);
-    }
-    D2MI_LAUNCH_CHECK();
-  }
+  if (p.reduce == kReduceNone) return 0;
+  const size_t total = (size_t)KH * KW * Cin * Cout;
+  const int accum = (flags & kPlanAccum) != 0;
+  if (p.reduce == kReduceFloat4)
+    hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3(p.reduce_grid), dim3(256), 0, st,
+                       reinterpret_cast<const float4*>(a.partial), a.splits, total / 4,
+                       reinterpret_cast<float4*>(dw_hwio), a.pbias, Cout, dbias, accum);
+  else
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(p.reduce_grid), dim3(256), 0, st, a.partial,
+                       a.splits, total, dw_hwio, a.pbias, Cout, dbias, accum);
+  D2MI_LAUNCH_CHECK();
   return 0;
 }
+
 
 extern "C" int d2mi_conv2d_wgrad(const float* x, const float* dy, float* dw_hwio, float* dbias,
                                  int N, int H, int W, int Cin, int Cout, int KH, int KW,

@@ -1,6 +1,7 @@
 // Library-internal host APIs shared between translation units.
 #pragma once
 #include "common.h"
+#include "tuning.h"
 
 namespace d2mi {
 
@@ -66,59 +67,16 @@ int topk_core_ex(const float* values, const int64_t* seg_start, const int32_t* s
                  int32_t* idx_out, int32_t* count_out, void* ws, size_t ws_bytes,
                  hipStream_t stream, bool sampled_floor = false);
 
-// Process-wide kernel-selection knobs (d2mi_set_tuning; initial values from
-// the environment): in-process A/B timing of kernel variants (tools/).
-// One line per knob: X(enum id, d2mi_set_tuning key, default).  The enum and
-// errors.hip's name and default arrays are generated from this list; the
-// environment variable is D2MI_<key in capitals>.
-// defaults: measured per shape and in the training step
-// conv_stream: the streaming 1x1 for launches of >= 8192 output pixels (r5 in-step A/B:
-// -0.85 %, profiles/r5_ab_inproc_conv_stream.log); roi_bwd_rec: run records (-0.41 %);
-// retina_fused: RetinaNet inference in four launches (retina_post.hip; 0 the
-// unfused pipeline, 2 the fused one with its in-workgroup exact select forced)
-// rpn_merge: the RPN's per-image concat + top-k as a merge rank (proposals.hip)
-// solo_mfma: the SOLOv2 Matrix-NMS intersections on int8 MFMA (solo.hip, r6):
-// 2 = bits expanded by an LDS table (default), 1 = by arithmetic, 0 = the AND +
-// popcount tiles; retina_var: the r6 RetinaNet post (compaction, early
-// select bound, DPP / permlane bitonic and select, NMS IoU only where boxes
-// meet, NMS tiles resolved as a ballot fixed point, the floor's radix select,
-// the rank launch's rounds looped, small levels' floor samples spread over the
-// level: 12018; 0 = the r5 form; + 4096, the rank
-// inside the NMS per 128-candidate window, is faster on iid logits and slower
-// on a model's head outputs, where the NMS needs several windows)
-#define D2MI_TUNE_KNOBS(X)                       \
-  X(kTuneConvWS, "conv_ws", 2)                   \
-  X(kTuneRoiFwd, "roi_fwd", -1)                  \
-  X(kTuneWgradWS, "wgrad_ws", 1)                 \
-  X(kTuneConvEpi, "conv_epi", 1)                 \
-  X(kTuneWgradWS1, "wgrad_ws1", 6)               \
-  X(kTuneWgradXCD, "wgrad_xcd", 1)               \
-  X(kTuneConvXCD, "conv_xcd", 1)                 \
-  X(kTuneWgradInc, "wgrad_inc", 1)               \
-  X(kTuneConvWSMinK, "conv_ws_mink", 16)         \
-  X(kTuneRoiPixGrid, "roi_pix_grid", 8192)       \
-  X(kTuneConvStream, "conv_stream", 8192)        \
-  X(kTuneRoiBwdRec, "roi_bwd_rec", 1)            \
-  X(kTuneRetinaFused, "retina_fused", 1)         \
-  X(kTuneRpnMerge, "rpn_merge", 1)               \
-  X(kTuneNmsScan, "nms_scan", 1)                 \
-  X(kTuneRoiHeavy, "roi_heavy", 16)              \
-  X(kTuneRpnCompact, "rpn_compact", 1)           \
-  X(kTuneConvStreamNt, "conv_stream_nt", 2)      \
-  X(kTuneConvNt, "conv_nt", 0)                   \
-  X(kTuneConvTailMinK, "conv_tail_mink", 8)      \
-  X(kTuneConvWSMinTiles, "conv_ws_mintiles", 0)  \
-  X(kTuneSgdRev, "sgd_rev", 0)                   \
-  X(kTuneRetinaRank, "retina_rank", 0)           \
-  X(kTuneSoloMfma, "solo_mfma", 2)               \
-  X(kTuneRetinaVar, "retina_var", 12018)
-enum TuneKey {
-#define X(id, key, def) id,
-  D2MI_TUNE_KNOBS(X)
-#undef X
-  kTuneCount
-};
-int tuning(TuneKey k);
+// The tuning knobs (D2MI_TUNE_KNOBS, tuning()): tuning.h.
+
+// A plan query's answer (d2mi_conv2d_plan and its kin): the n integers of v
+// into out.  Returns n, or -1 when out_len is short.
+inline int emit_plan(const int32_t* v, int n, int32_t* out, int out_len) {
+  D2MI_REQUIRE(out != nullptr && out_len >= n, "plan query: out_len %d is short of the plan's %d integers",
+               out_len, n);
+  for (int i = 0; i < n; ++i) out[i] = v[i];
+  return n;
+}
 
 // Byte fill by a kernel launch on st (never hipMemsetAsync: errors.hip).
 // 0 on success.

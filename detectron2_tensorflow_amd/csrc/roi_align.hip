@@ -1558,13 +1558,10 @@ int roi_bwd_core(const RoiArgs* sets, int nsets, const int32_t* dims, int num_le
   const long long wg_max = std::max(1, tuning(kTuneRoiPixGrid));
   const dim3 grid((unsigned)std::max(1LL, std::min((cap + 3) / 4, wg_max)));
   if (vec4 && C == 256) {
-    static const int ppw = [] {
-      const char* e = getenv("D2MI_ROI_BWD_PPW");
-      return e && e[0] == '8' ? 8 : 0;
-    }();
+    const int ppw = tuning(kTuneRoiBwdPpw);
     // tuning "roi_bwd_rec" (the run-record pass): 1 two pixels per wave, 4
     // rows in flight per lane (r5c, default); 2 / 3 four pixels per wave with
-    // 2 / 4 rows (r5b: 4); 5 one pixel per wave, 8 rows; D2MI_ROI_BWD_PPW=8
+    // 2 / 4 rows (r5b: 4); 5 one pixel per wave, 8 rows; tuning "roi_bwd_ppw" = 8
     // eight pixels per wave (A/B forms)
     const int tv = tuning(kTuneRoiBwdRec);
     const int pw = ppw == 8 ? 8 : tv == 5 ? 1 : (tv == 2 || tv == 3) ? 4 : 2;  // pixels per wave

@@ -744,8 +744,8 @@ int topk_core_ex(const float* values, const int64_t* seg_start, const int32_t* s
   hipLaunchKernelGGL(topk_init_kernel, dim3(kRep, S), dim3(256), 0, stream, st, hist, seg_len,
                      seg_k, k);
   D2MI_LAUNCH_CHECK();
-  static const char* floor_env = getenv("D2MI_TOPK_FLOOR");  // "0": radix passes only (A/B)
-  if (sampled_floor && key_mode == 1 && max_len > kCap && !(floor_env && floor_env[0] == '0')) {
+  // (tuning "topk_floor" = 0: radix passes only, A/B)
+  if (sampled_floor && key_mode == 1 && max_len > kCap && tuning(kTuneTopkFloor) != 0) {
     const int runs = (max_len + kSampleStride - 1) / kSampleStride;
     hipLaunchKernelGGL(topk_sample_kernel, dim3((runs + kSampleRunsPerWg - 1) / kSampleRunsPerWg, S),
                        dim3(kThreads), 0, stream, values, seg_start, seg_len, st, hist);

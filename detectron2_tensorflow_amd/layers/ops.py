@@ -908,6 +908,75 @@ def conv2d_wgrad(x, dy, kernel_size, stride=1, pad=(0, 0), with_bias=False, math
     return (dw, db) if with_bias else dw
 
 
+# ------------------------------------------------------------- plan queries
+# The launch plans of the three conv families as dicts (d2mi_conv2d_plan and
+# its kin, include/d2mi.h: the planner the launchers run; no GPU needed).
+# operands: the OP_* facts about a launch's pointers; workspace_bytes None =
+# the shape's own *_workspace_size.
+OP_TOPDOWN, OP_RESIDUAL, OP_GATE, OP_ALIGNED, OP_BIAS_ALIGNED, OP_WORKSPACE, OP_WS_ALIGNED = (
+    1, 2, 4, 8, 16, 32, 64)
+OP_ALL_ALIGNED = OP_ALIGNED | OP_BIAS_ALIGNED | OP_WS_ALIGNED
+CONV_FAMILIES = ("tiled128x128", "tiled128x64", "tiled128x32", "ws256x128", "stream1x1")
+WGRAD_KERNELS = ("f32", "split", "split_occ3", "ws", "ws_inc", "ws2")
+_LAUNCH_FIELDS = ("tile0", "tiles", "splits", "kt_per_split", "m_base", "m_end", "reduce",
+                  "reduce_grid")
+CONV_PLAN_FIELDS = (("family", "occ", "split3", "lds_epi", "M", "BM", "BN", "nM", "nN", "nk")
+                    + tuple("main_" + f for f in _LAUNCH_FIELDS)
+                    + tuple("tail_" + f for f in _LAUNCH_FIELDS)
+                    + ("stream_kmax", "stream_tn", "stream_form", "stream_nslices", "stream_grid"))
+LEVELS_PLAN_FIELDS = ("family", "occ", "split3", "lds_epi", "BM", "BN", "nN", "nk", "tiles",
+                      "splits", "kt_per_split", "reduce_grid", "nlev")
+WGRAD_PLAN_FIELDS = ("kernel", "TM", "TN", "BM", "BN", "nCi", "nCo", "tiles", "nchunks", "splits",
+                     "chunks_per_split", "part", "reduce", "reduce_grid")
+
+
+def _plan_query(fn, name, args, flags, operands, workspace_bytes, n):
+    out = (_C.ctypes.c_int32 * n)()
+    rc = fn(*args, int(flags), int(operands), int(workspace_bytes), out, n)
+    _C.check(min(rc, 0), name)
+    v = list(out)
+    return v[:-2], v[-2] | (v[-1] << 31)
+
+
+def conv_plan(N, H, W, Cin, Cout, k, stride=1, pad=(0, 0), flags=4,
+              operands=OP_ALL_ALIGNED | OP_WORKSPACE, workspace_bytes=None):
+    """The plan of conv2d_nhwc for a shape (flags: d2mi_conv2d_nhwc_ex's, 4 = split math)."""
+    args = (N, H, W, Cin, Cout, k, k, int(stride), int(pad[0]), int(pad[1]))
+    lib = _C.lib()
+    if workspace_bytes is None:
+        workspace_bytes = lib.d2mi_conv2d_workspace_size(*args)
+    v, wsb = _plan_query(lib.d2mi_conv2d_plan, "d2mi_conv2d_plan", args, flags, operands,
+                         workspace_bytes, len(CONV_PLAN_FIELDS) + 2)
+    return dict(zip(CONV_PLAN_FIELDS, v), workspace_bytes=wsb)
+
+
+def conv_levels_plan(dims, Cin, Cout, k, stride=1, pad=(0, 0), flags=4,
+                     operands=OP_ALL_ALIGNED | OP_WORKSPACE, workspace_bytes=None):
+    """The plan of conv2d_nhwc_levels; dims: (N, H, W) per level."""
+    dm = _C.host_array(_C.ctypes.c_int32, [int(d) for lv in dims for d in lv])
+    args = (dm, len(dims), Cin, Cout, k, k, int(stride), int(pad[0]), int(pad[1]))
+    lib = _C.lib()
+    if workspace_bytes is None:
+        workspace_bytes = lib.d2mi_conv2d_levels_workspace_size(*args)
+    v, wsb = _plan_query(lib.d2mi_conv2d_levels_plan, "d2mi_conv2d_levels_plan", args, flags,
+                         operands, workspace_bytes, len(LEVELS_PLAN_FIELDS) + 16)
+    n = len(LEVELS_PLAN_FIELDS)
+    return dict(zip(LEVELS_PLAN_FIELDS, v), tile0=v[n:n + 7], moff=v[n + 7:n + 14],
+                workspace_bytes=wsb)
+
+
+def wgrad_plan(N, H, W, Cin, Cout, k, stride=1, pad=(0, 0), flags=4,
+               operands=OP_ALL_ALIGNED | OP_WORKSPACE, workspace_bytes=None):
+    """The plan of conv2d_wgrad (flags: d2mi_conv2d_wgrad_ex's, 4 = split math, 8 = accumulate)."""
+    args = (N, H, W, Cin, Cout, k, k, int(stride), int(pad[0]), int(pad[1]))
+    lib = _C.lib()
+    if workspace_bytes is None:
+        workspace_bytes = lib.d2mi_conv2d_wgrad_workspace_size(*args)
+    v, wsb = _plan_query(lib.d2mi_conv2d_wgrad_plan, "d2mi_conv2d_wgrad_plan", args, flags,
+                         operands, workspace_bytes, len(WGRAD_PLAN_FIELDS) + 2)
+    return dict(zip(WGRAD_PLAN_FIELDS, v), workspace_bytes=wsb)
+
+
 # ---------------------------------------------------------- FrozenBN fold
 class _FoldFrozenBNFn(torch.autograd.Function):
     """(w_eff, b_eff, packed) = conv weights with a frozen BatchNorm folded in

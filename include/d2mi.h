@@ -91,7 +91,25 @@ const char* d2mi_last_error(void);
  *                  by a workgroup radix select, 32 = the rank launch's search
  *                  rounds capped and looped, 2 = a small level's floor
  *                  samples spread over the level, 4 = floor and finish
- *                  launched twice (measurement only). */
+ *                  launched twice (measurement only);
+ *   "conv_occ"     resident workgroups per CU of the 128x128 conv kernel: 3
+ *                  (default), 2 = two;
+ *   "conv_split_slots" split-K workgroup target of the convs (0 = the plan's
+ *                  own: two per CU, one for the WS conv);
+ *   "conv_tail"    tail tiles of a mostly empty last round split along K (1);
+ *                  0 = off;
+ *   "wgrad_occ"    the 128x128 split weight gradient at three workgroups per
+ *                  CU from "wgrad_occ3_min_p" pixels (65536) up: 3 (default),
+ *                  2 = two everywhere;
+ *   "wgrad_slots"  pixel-split workgroup target of the weight gradient (0 =
+ *                  the plan's own: 256 / 512 / 768 by kernel);
+ *   "wgrad_minch"  fewest 32-pixel chunks per split (16; <= 0 = the default);
+ *   "wgrad_maxsplit" most pixel splits (128; <= 0 = the default);
+ *   "wgrad_prio"   wave priority 1 while issuing MFMAs in the weight gradient
+ *                  (1 on);
+ *   "roi_bwd_ppw"  ROIAlign backward pixel pass: 8 = eight pixels per wave (0);
+ *   "topk_floor"   sampled-floor first pass of the segmented top-k (1); 0 =
+ *                  radix passes only. */
 int d2mi_set_tuning(const char* key, int value);
 /* Current value of a d2mi_set_tuning key (INT32_MIN for an unknown key). */
 int d2mi_get_tuning(const char* key);
@@ -494,6 +512,32 @@ int d2mi_conv2d_nhwc(const float* x, const float* w_packed, const float* bias,
  * workgroups and reduce in a fixed order (deterministic). */
 size_t d2mi_conv2d_workspace_size(int N, int H, int W, int Cin, int Cout, int KH, int KW,
                                   int stride, int pad_beg, int pad_end);
+/* The launch plan of d2mi_conv2d_nhwc_ex / _gated for a shape, as integers;
+ * launches nothing (the same planner the launcher runs, and the device's CU
+ * count -- 256 without a device).  flags: d2mi_conv2d_nhwc_ex's.  operands,
+ * the facts about the pointers a launch would get (a null one counts as
+ * aligned): 1 top-down, 2 residual, 4 gate present; 8 = y and the present
+ * top-down / residual / gate are 16-byte aligned; 16 = the bias is; 32 = a
+ * workspace is passed, of workspace_bytes; 64 = it is 16-byte aligned.
+ * Writes 33 integers to out and returns 33; negative (d2mi_last_error) when
+ * the launcher would refuse the shape or out_len is short:
+ *   [0] family: 0 tiled 128x128, 1 128x64, 2 128x32, 3 warp-specialised
+ *       256x128, 4 streaming 1x1;  [1] resident workgroups per CU;
+ *   [2] split products;  [3] LDS epilogue usable;  [4] M = N*OH*OW;
+ *   [5] BM  [6] BN  [7] nM  [8] nN  [9] nk (k-steps);
+ *   [10..17] main launch: first tile, tiles, splits (grid = tiles x splits),
+ *       k-steps per split, first row, end row, reduce (0 none, 1 scalar,
+ *       2 float4), reduce grid;   [18..25] tail launch, the same (tiles 0:
+ *       none);  under family 4 these describe the tiled kernels' plan, which
+ *       is not launched;
+ *   [26..30] streaming kernel: KMAX, TN, form (1 residual | 2 gate), slices,
+ *       grid (workgroups of 512 threads); 0 otherwise;
+ *   [31] + [32] * 2^31 = workspace bytes the plan carves: the main launch's
+ *       slab, then the tail launch's, [splits][rows][Cout] floats each.
+ * A missing or short workspace gives the one-pass plan. */
+int d2mi_conv2d_plan(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                     int pad_beg, int pad_end, int flags, int operands, size_t workspace_bytes,
+                     int32_t* out, int out_len);
 int d2mi_conv2d_nhwc_ex(const float* x, const float* w_packed, const float* bias,
                         const float* topdown, const float* residual, float* y, int N, int H,
                         int W, int Cin, int Cout, int KH, int KW, int stride, int pad_beg,
@@ -524,6 +568,17 @@ int d2mi_conv2d_nhwc_gated(const float* x, const float* w_packed, const float* b
  * d2mi_conv2d_levels_workspace_size bytes; fixed-order reduce). */
 size_t d2mi_conv2d_levels_workspace_size(const int32_t* dims, int nlev, int Cin, int Cout,
                                          int KH, int KW, int stride, int pad_beg, int pad_end);
+/* The plan of d2mi_conv2d_nhwc_levels, as d2mi_conv2d_plan (operands: 8 =
+ * every level's output is 16-byte aligned, 32 / 64 the workspace).  29 integers:
+ *   [0] family (0..2)  [1] resident workgroups per CU  [2] split products
+ *   [3] LDS epilogue  [4] BM  [5] BN  [6] nN  [7] nk  [8] tiles  [9] splits
+ *   (grid = tiles x splits)  [10] k-steps per split  [11] reduce grid (0: no
+ *   reduce)  [12] nlev  [13..19] first tile of each level, [nlev] = tiles
+ *   [20..26] first slab row of each level, [26] = all rows
+ *   [27] + [28] * 2^31 = workspace bytes ([splits][rows][Cout] floats). */
+int d2mi_conv2d_levels_plan(const int32_t* dims, int nlev, int Cin, int Cout, int KH, int KW,
+                            int stride, int pad_beg, int pad_end, int flags, int operands,
+                            size_t workspace_bytes, int32_t* out, int out_len);
 int d2mi_conv2d_nhwc_levels(const float* const* xs, const int32_t* dims, int nlev,
                             const float* w_packed, const float* bias, float* const* ys, int Cin,
                             int Cout, int KH, int KW, int stride, int pad_beg, int pad_end,
@@ -546,6 +601,20 @@ int d2mi_split_bf16x3(const float* x, int64_t n, uint16_t* out, void* stream);
  * pixel reduction is split over workgroups and summed in a fixed order. */
 size_t d2mi_conv2d_wgrad_workspace_size(int N, int H, int W, int Cin, int Cout, int KH, int KW,
                                         int stride, int pad_beg, int pad_end);
+/* The plan of d2mi_conv2d_wgrad_ex (flags: its flags), as d2mi_conv2d_plan
+ * (operands: 8 = dw is 16-byte aligned, 32 / 64 the workspace).  16 integers:
+ *   [0] kernel: 0 f32 <TM,TN>, 1 split <TM,TN>, 2 split 128x128 at three
+ *       workgroups per CU, 3 warp-specialised, 4 the same with the incremental
+ *       pixel cursor, 5 the same loading two chunks ahead;
+ *   [1] TM  [2] TN  [3] BM  [4] BN  [5] Cin tiles  [6] Cout tiles  [7] tiles
+ *   [8] 32-pixel chunks  [9] splits (grid = tiles x splits)  [10] chunks per
+ *   split  [11] slabs are written (splits > 1 or accumulating)  [12] reduce
+ *   (0 none, 1 scalar, 2 float4)  [13] reduce grid
+ *   [14] + [15] * 2^31 = workspace bytes: [splits] dw slabs, then [splits]
+ *   dbias slabs. */
+int d2mi_conv2d_wgrad_plan(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                           int pad_beg, int pad_end, int flags, int operands,
+                           size_t workspace_bytes, int32_t* out, int out_len);
 int d2mi_conv2d_wgrad(const float* x, const float* dy, float* dw_hwio, float* dbias, int N,
                       int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_beg,
                       int pad_end, void* workspace, size_t workspace_bytes, void* stream);

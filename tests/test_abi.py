@@ -125,6 +125,9 @@ TUNING_DEFAULTS = {
     "roi_bwd_rec": 1, "retina_fused": 1, "rpn_merge": 1, "nms_scan": 1, "roi_heavy": 16,
     "rpn_compact": 1, "conv_stream_nt": 2, "conv_nt": 0, "conv_tail_mink": 8,
     "conv_ws_mintiles": 0, "sgd_rev": 0, "retina_rank": 0, "solo_mfma": 2, "retina_var": 12018,
+    "conv_occ": 3, "conv_split_slots": 0, "conv_tail": 1, "wgrad_occ": 3, "wgrad_occ3_min_p": 65536,
+    "wgrad_slots": 0, "wgrad_minch": 16, "wgrad_maxsplit": 128, "wgrad_prio": 1, "roi_bwd_ppw": 0,
+    "topk_floor": 1,
 }
 
 _TUNING_CHILD = """
@@ -156,13 +159,15 @@ def _tuning_in_child(extra_env):
 
 
 def test_tuning_defaults_and_environment_without_gpu():
-    """The 25 knobs' defaults, their D2MI_<KEY> environment variables, and unknown keys."""
+    """The 36 knobs' defaults, their D2MI_<KEY> environment variables, and unknown keys."""
     from detectron2_tensorflow_amd import _build
     _build.build()
     got = _tuning_in_child({})
     assert got.pop("<unknown get>") == -2 ** 31
     assert "unknown tuning key" in got.pop("<unknown set>")
-    assert got == TUNING_DEFAULTS
-    got = _tuning_in_child({"D2MI_CONV_NT": "1", "D2MI_RETINA_VAR": "0"})
+    assert got == TUNING_DEFAULTS and len(got) == 36
+    # (D2MI_CONV_TAIL, D2MI_WGRAD_MAXSPLIT: read by bare getenv before they joined the table)
+    got = _tuning_in_child({"D2MI_CONV_NT": "1", "D2MI_RETINA_VAR": "0", "D2MI_CONV_TAIL": "0",
+                            "D2MI_WGRAD_MAXSPLIT": "4"})
     assert got.pop("<unknown get>") == -2 ** 31 and "unknown tuning key" in got.pop("<unknown set>")
-    assert got == dict(TUNING_DEFAULTS, conv_nt=1, retina_var=0)
+    assert got == dict(TUNING_DEFAULTS, conv_nt=1, retina_var=0, conv_tail=0, wgrad_maxsplit=4)

@@ -775,7 +775,7 @@ def test_conv2d_split_bf16_products_are_f32_class(dev, shape):
     ((2, 33, 40, 128, 512), "gr"), ((2, 33, 40, 128, 128), "plain"), ((1, 29, 31, 128, 192), "r"),
     ((2, 20, 24, 256, 1024), "gr"), ((2, 20, 24, 256, 256), "g"), ((1, 21, 23, 256, 64), "plain"),
     # K = 256 at >= 32 k pixels into 64 / 512 channels: the stream kernel's
-    # K = 256 variant ON BY DEFAULT (stream1x1_variant: stream256_shape), whose
+    # K = 256 variant ON BY DEFAULT (plan_conv: stream256), whose
     # tiled fallback keeps its tail tiles' K whole -- the shapes above stay
     # under 32 k pixels, where both arms run the tiled kernel
     ((2, 128, 160, 256, 64), "r"), ((2, 128, 160, 256, 64), "g"),
@@ -1224,6 +1224,18 @@ def test_conv2d_tail_split_matches_float64(dev, epi, C):
     np.testing.assert_allclose(y.cpu().double().numpy(), ref.numpy(), rtol=1e-4, atol=1e-4)
     # the tail rows (the last 14 tiles) are really there
     assert torch.isfinite(y[-1, -1]).all() and float(y[-1, -1].abs().sum()) > 0
+    # tuning "conv_tail" = 0 in-process (once environment-only): the same conv
+    # without the tail launch, the same bound
+    assert ops().conv_plan(N, H, W, C, C, 3, pad=(1, 1))["tail_tiles"] > 0
+    try:
+        ops().set_tuning("conv_tail", 0)
+        assert ops().conv_plan(N, H, W, C, C, 3, pad=(1, 1))["tail_tiles"] == 0
+        y0 = ops().conv2d_nhwc(t(x), ops().pack_conv_weights(t(w)), t(b), 1, (1, 1),
+                               relu=epi == "relu", residual=t(res), topdown=t(top))
+    finally:
+        ops().set_tuning("conv_tail", 1)
+    np.testing.assert_allclose(y0.cpu().double().numpy(), ref.numpy(), rtol=1e-4, atol=1e-4)
+    assert float(y0[-1, -1].abs().sum()) > 0
 
 
 @pytest.mark.parametrize("shape", [(2, 50, 84, 256, 64, 1), (2, 25, 42, 512, 2048, 1),
