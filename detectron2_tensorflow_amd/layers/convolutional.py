@@ -135,28 +135,18 @@ def _wgrad(x, gy, w_shape, stride, pb, pe, want_bias=False, accumulate_into=None
 
 def _wgrad_shared(acc, x, gy, w_shape, stride, pb, pe, want_bias):
     """One call's share of a weight used by several calls of one forward
-    (``wacc`` = {"n": calls, "k": done}: the RPN head's 3x3 over the FPN
+    (``wacc``, a handoff.LevelAccumulator: the RPN head's 3x3 over the FPN
     levels): its (gw, gb) go into the accumulator (the reduce pass adds them:
     old + new, autograd's order for the summed gradients); every call but the
     last returns (None, None), the last the sums."""
-    acc["k"] += 1
-    if acc["k"] == 1:
-        # every call's backward must run in this pass, else the gradient
-        # never leaves and a stale buffer would poison a later backward
-        handoff.expect_complete(acc, lambda a: a["k"] == 0,
-                                lambda a: (a.pop("buf", None), a.__setitem__("k", 0)),
-                                "shared conv weight-gradient calls")
-    buf = acc.get("buf")
-    gw, gb = _wgrad(x, gy, w_shape, stride, pb, pe, want_bias, accumulate_into=buf)
-    if want_bias and gb is None:
-        cs = ops.column_sum(gy)
-        gb = cs if buf is None or buf[1] is None else buf[1].add_(cs)
-    acc["buf"] = (gw, gb)
-    if acc["k"] < acc["n"]:
-        return None, None
-    acc.pop("buf")
-    acc["k"] = 0  # (a second backward of the same graph starts over)
-    return gw, gb
+    def step(buf):
+        gw, gb = _wgrad(x, gy, w_shape, stride, pb, pe, want_bias, accumulate_into=buf)
+        if want_bias and gb is None:
+            cs = ops.column_sum(gy)
+            gb = cs if buf is None or buf[1] is None else buf[1].add_(cs)
+        return gw, gb
+
+    return acc.accumulate(step) or (None, None)
 
 
 # r6: {"stream": a side stream} while the graphed training step captures its
@@ -171,8 +161,9 @@ WGRAD_STREAM = {}
 def _wgrad_of(ctx, x, gy, w, stride, pb, pe, want_b):
     """(weight, bias) gradient of _ConvMFMAFn's backward, None where not needed."""
     gw = gb = None
-    if ctx.needs_input_grad[1] and ctx.wacc is not None:
-        gw, gb = _wgrad_shared(ctx.wacc, x, gy, w.shape, stride, pb, pe, want_b)
+    wacc = ctx.links.wacc if ctx.links is not None else None
+    if ctx.needs_input_grad[1] and wacc is not None:
+        gw, gb = _wgrad_shared(wacc, x, gy, w.shape, stride, pb, pe, want_b)
     else:
         if ctx.needs_input_grad[1]:
             gw, gb = _wgrad(x, gy, w.shape, stride, pb, pe, want_b)
@@ -187,32 +178,16 @@ def _gate_eligible(w_shape, stride, pb, pe):
 
 
 class _ConvMFMAFn(torch.autograd.Function):
-    """Fused-ReLU chains: a conv with a fused ReLU tags its output.  A consumer
-    conv called with gate_input=True (the caller's declaration that it is the
-    SOLE consumer of that ReLU output: the bottleneck's conv2 / conv3, the mask
-    head's conv chain and deconv) applies the producer's ReLU mask in its own
-    dgrad epilogue (kMaskByResidual) and flags it; the producer then skips its
-    threshold_backward.  Without the declaration nothing is fused.
-
-    Residual-gradient hand-off (the bottleneck's identity shortcut): the conv
-    that adds ``residual`` is given a dict ``res_grad_to`` and the conv that
-    reads the same tensor as its input the same dict as ``grad_from``.  The
-    adder's backward (always first: the reader's backward waits for the chain
-    in between) leaves the residual's gradient there instead of returning
-    it, and the reader adds it inside its dgrad epilogue -- before the ReLU
-    gate, so  gx = (dgrad + g_res) * (x > 0)  is one pass and autograd never
-    materialises the sum.
-
-    Pair hand-off (``pair_grad``: the bottleneck's conv1 and projection
-    shortcut, both reading x): whichever backward runs first leaves its input
-    gradient in the shared dict and returns none for x; the second adds it in
-    its own dgrad epilogue / stride scatter and returns the sum.  Both always
-    run once the block output has a gradient (each feeds it)."""
+    """The MFMA conv with its fused epilogue (bias, ReLU, top-down / residual
+    add).  ``links`` (a handoff.Links or None) holds this call's ends of the
+    gradient hand-offs of the training graph -- the sole-consumer ReLU gate,
+    the residual link, the pair, the join, the level accumulator: see
+    layers/handoff.py.  The backward asks it what to do with the input
+    gradient (Links.plan) and makes one _dgrad call from the answer."""
 
     @staticmethod
-    def forward(ctx, x, w_hwio, bias, w_packed, stride, pads, relu, topdown, residual=None,
-                relu_after=False, gate_input=False, res_grad_to=None, grad_from=None,
-                pair_grad=None, join=None, wacc=None):
+    def forward(ctx, x, w_hwio, bias, w_packed, stride, pads, relu, topdown=None, residual=None,
+                relu_after=False, links=None):
         has_add = topdown is not None or residual is not None
         if relu and has_add and not relu_after:
             raise ValueError("relu(conv) + add is not differentiable here; use relu_after_add")
@@ -220,35 +195,21 @@ class _ConvMFMAFn(torch.autograd.Function):
                             relu_after_add=relu_after)
         ctx.save_for_backward(x, w_hwio, y if relu else None)
         ctx.conf = (stride, pads, relu, bias is not None, topdown is not None, residual is not None)
-        ctx.in_info = getattr(x, "_d2mi_relu_info", None) if gate_input else None
-        ctx.res_grad_to = res_grad_to if residual is not None else None
-        ctx.grad_from = grad_from
-        ctx.pair_grad = pair_grad
-        # FPN top-down hand-off (modeling/necks/fpn.py TD_HANDOFF): the merged
-        # map's output conv (pair_grad {"td": True}) and the finer lateral that
-        # reads it as its top-down input -- both MFMA convs, registered here
-        if pair_grad is not None and pair_grad.get("td"):
-            pair_grad["mfma"] = True
-        tdp = getattr(topdown, "_d2mi_td_pair", None) if topdown is not None else None
-        ctx.td_pair = (tdp if tdp is not None and tdp.get("mfma") and topdown.requires_grad
-                       else None)
-        if ctx.td_pair is not None:
-            ctx.td_pair["lat_mfma"] = True
-        ctx.join = join
-        ctx.wacc = wacc  # a weight shared by several calls: _wgrad_shared
-        # the producer's ReLU tag, used if a join is registered by backward time
-        ctx.relu_cand = getattr(x, "_d2mi_relu_info", None)
-        ctx.out_info = None
+        ctx.links = links
+        if links is not None:
+            links.bind(x, topdown, residual is not None)
+        ctx.out_tag = None
         if relu:  # (forward runs with grad mode off: tag unconditionally)
-            ctx.out_info = {"masked": False}
-            y._d2mi_relu_info = ctx.out_info
+            ctx.out_tag = handoff.ReluTag()
+            handoff.tag(y, handoff.RELU, ctx.out_tag)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, w, y = ctx.saved_tensors
         stride, (pb, pe), relu, has_bias, has_td, has_res = ctx.conf
-        if relu and not (ctx.out_info is not None and ctx.out_info["masked"]):
+        links = ctx.links
+        if relu and not (ctx.out_tag is not None and ctx.out_tag.masked):
             # relu is the last op whenever an add is fused (relu_after)
             gy = torch.ops.aten.threshold_backward(gy, y, 0.0)
         gtd = None
@@ -258,19 +219,15 @@ class _ConvMFMAFn(torch.autograd.Function):
             N, OH, OW, C = gy.shape
             g = F.pad(gy, (0, 0, 0, OW % 2, 0, OH % 2))
             gtd = g.reshape(N, (OH + 1) // 2, 2, (OW + 1) // 2, 2, C).sum((2, 4))
-        if gtd is not None and ctx.td_pair is not None and ctx.needs_input_grad[7]:
+        if (gtd is not None and links is not None and links.td_pair is not None
+                and ctx.needs_input_grad[7]):
             # the merged map's other reader is its output conv: first of the
             # two leaves its gradient, the second adds it (the output conv in
             # its dgrad epilogue) -- autograd's sum of the two, no add launch
-            other = ctx.td_pair.pop("g", None)
-            if other is None:
-                handoff.deposit(ctx.td_pair, "g", gtd, "FPN top-down")
-                gtd = None
-            else:
-                gtd = gtd + other
+            gtd = links.td_pair.meet_topdown(gtd)
         gres = gy if has_res and ctx.needs_input_grad[8] else None
-        if gres is not None and ctx.res_grad_to is not None:
-            handoff.deposit(ctx.res_grad_to, "g", gres, "residual")  # taken by the conv reading it
+        if gres is not None and links is not None and links.res_grad_to is not None:
+            links.res_grad_to.put(gres)  # taken by the conv reading it
             gres = None
         gx = gw = gb = None
         want_b = has_bias and ctx.needs_input_grad[2]
@@ -284,45 +241,13 @@ class _ConvMFMAFn(torch.autograd.Function):
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 gw, gb = _wgrad_of(ctx, x, gy, w, stride, pb, pe, want_b)
-        if ctx.needs_input_grad[0] and _join_active(ctx):
-            gx = _join_backward(ctx, gy, x, w, stride, pb, pe)
+        if ctx.needs_input_grad[0] and links is None:
+            gx = _dgrad(gy, w, x.shape, stride, pb, pe)
         elif ctx.needs_input_grad[0]:
-            add = ctx.grad_from.pop("g", None) if ctx.grad_from is not None else None
-            pair = ctx.pair_grad
-            if pair is not None and pair.get("td") and not pair.get("lat_mfma"):
-                pair = None  # (an FPN output conv whose map no MFMA lateral reads)
-            deposit = False
-            deferred = None
-            gated = ctx.in_info is not None and _gate_eligible(w.shape, stride, pb, pe)
-            if pair is not None:
-                other = pair.pop("g", None)
-                if isinstance(other, ops.DeferredPixels):
-                    # the ROI poolers' pixel pass of this level, run into this
-                    # dgrad's full map afterwards (no add here); a gated or
-                    # already-adding dgrad takes the pooled map instead
-                    if add is None and not gated:
-                        deferred, other = other, None
-                    else:
-                        other = other.materialize()
-                if other is None and deferred is None:
-                    deposit = True  # first of the pair: no gate, no add
-                elif other is None:
-                    pass
-                elif add is None:
-                    add = other
-                else:
-                    add = add + other
-            info = None if deposit else ctx.in_info
-            if info is not None and _gate_eligible(w.shape, stride, pb, pe):
-                gx = _dgrad(gy, w, x.shape, stride, pb, pe, relu_gate=x, add=add)
-                info["masked"] = True
-            else:
-                gx = _dgrad(gy, w, x.shape, stride, pb, pe, add=add)
-            if deferred is not None:
-                gx = deferred.add_into(gx.contiguous())
-            if deposit:
-                handoff.deposit(pair, "g", gx, "pair")
-                gx = None
+            plan = links.plan(_gate_eligible(w.shape, stride, pb, pe))
+            gx = plan.finish(_dgrad(gy, w, x.shape, stride, pb, pe,
+                                    relu_gate=x if plan.gate else None,
+                                    add=plan.add, add2=plan.add2))
         if main is not None:
             main.wait_stream(side)
             for t in (gw, gb):  # (made on the side stream, used on this one)
@@ -330,61 +255,14 @@ class _ConvMFMAFn(torch.autograd.Function):
                     t.record_stream(main)
         else:
             gw, gb = _wgrad_of(ctx, x, gy, w, stride, pb, pe, want_b)
-        return (gx, gw, gb, None, None, None, None, gtd, gres, None, None, None, None, None, None,
-                None)
+        return gx, gw, gb, None, None, None, None, gtd, gres, None, None
 
 
-def _join_active(ctx):
-    p = ctx.join if ctx.join is not None else ctx.pair_grad
-    return p is not None and p.get("join", False) and ctx.grad_from is None
-
-
-def _join_backward(ctx, gy, x, w, stride, pb, pe):
-    """Input gradient of a conv in a three-consumer join: a ReLU output x (a
-    ResNet stage output) read by the next stage's conv1 / projection-shortcut
-    pair AND by the FPN lateral (``join``, registered by the FPN forward in
-    the pair's dict).  Autograd would form  lat + (pair2 + pair1)  and then
-    the producer's threshold_backward; here
-      * the first pair member deposits its gradient ("g", as without a join);
-      * the second pair member forms  s = dgrad + g ; if the lateral's
-        gradient is already there it returns  gate((s) + lat)  (one scatter
-        pass for a strided 1x1), else it deposits s ("sum");
-      * the lateral returns  gate(dgrad + s)  if s is there, else it deposits
-        its own dgrad ("lat").
-    The last one applies the producer's ReLU mask in the same pass and flags
-    it (the producer then skips its threshold_backward), so the sum and the
-    gate are bit-identical to the autograd formulation.  Members that
-    deposit return None for x."""
-    info = ctx.relu_cand
-    if ctx.join is not None:  # the lateral
-        p = ctx.join
-        s = p.pop("sum", None)
-        if s is None:
-            handoff.deposit(p, "lat", _dgrad(gy, w, x.shape, stride, pb, pe), "join (lateral)")
-            return None
-        p["last"] = "lateral"  # (tests: which member completed the join)
-        if info is not None and _gate_eligible(w.shape, stride, pb, pe):
-            gx = _dgrad(gy, w, x.shape, stride, pb, pe, relu_gate=x, add=s)
-            info["masked"] = True
-            return gx
-        return _dgrad(gy, w, x.shape, stride, pb, pe, add=s)
-    p = ctx.pair_grad
-    other = p.pop("g", None)
-    if isinstance(other, ops.DeferredPixels):
-        other = other.materialize()
-    if other is None:  # first of the pair
-        handoff.deposit(p, "g", _dgrad(gy, w, x.shape, stride, pb, pe), "join (pair)")
-        return None
-    lat = p.pop("lat", None)
-    if lat is None:
-        handoff.deposit(p, "sum", _dgrad(gy, w, x.shape, stride, pb, pe, add=other), "join (sum)")
-        return None
-    p["last"] = "pair"
-    gate = x if info is not None else None
-    gx = _dgrad(gy, w, x.shape, stride, pb, pe, relu_gate=gate, add=other, add2=lat)
-    if info is not None:
-        info["masked"] = True
-    return gx
+def _conv_mfma(x, w_hwio, bias, w_packed, stride, pads, relu, topdown=None, residual=None,
+               relu_after=False, links=None):
+    """_ConvMFMAFn.apply with keywords (Function.apply takes none)."""
+    return _ConvMFMAFn.apply(x, w_hwio, bias, w_packed, stride, pads, relu, topdown, residual,
+                             relu_after, links)
 
 
 class FoldGroup:
@@ -651,7 +529,10 @@ class Conv2D(Layer):
         """topdown: fused + up2(topdown) (FPN merge); residual: fused + residual;
         relu_after_add: the layer's ReLU runs after those adds; final_relu: an
         extra ReLU after the adds for a layer without activation (the
-        bottleneck's relu(conv3(x) + shortcut), blocks.py:143-186)."""
+        bottleneck's relu(conv3(x) + shortcut), blocks.py:143-186).
+        relu_input_sole_consumer, res_grad_to / grad_from (a handoff.Slot),
+        pair_grad / join (a handoff.Pair), wacc (a handoff.LevelAccumulator):
+        the gradient hand-offs of layers/handoff.py."""
         impl = self.impl
         if impl == "auto":
             impl = "mfma" if self._mfma_eligible(inputs) else "torch"
@@ -676,17 +557,17 @@ class Conv2D(Layer):
                 if padc or not torch.is_grad_enabled():
                     join = None  # (a padded input is another tensor: no join)
                 else:
-                    join["join"] = True  # the pair members now leave their sum to this layer
+                    join.join_lateral()  # the pair members now leave their sum to this layer
             if padc:
                 inputs = F.pad(inputs, (0, padc))
                 w = F.pad(w, (0, 0, 0, padc))
                 packed = None
             if packed is None:
                 packed = self.packed_weights(w)
+            links = handoff.Links(bool(relu_input_sole_consumer), res_grad_to, grad_from,
+                                  pair_grad, join, wacc)
             ret = _ConvMFMAFn.apply(inputs, w, b, packed, self.stride, pads,
-                                    fuse_relu, topdown, residual, relu_after_add,
-                                    bool(relu_input_sole_consumer), res_grad_to, grad_from,
-                                    pair_grad, join, wacc)
+                                    fuse_relu, topdown, residual, relu_after_add, links)
             if raw:  # the conv (+ bias) alone: the caller applies the normalizer / activation
                 return ret
             if norm is not None and is_relu(self.act_fn) and hasattr(norm, "fused_ok") \
@@ -737,7 +618,7 @@ class DeformConv2D(Conv2D):
     gather, d2mi_deform_sample_fwd) -> the main product as a 1x1 MFMA conv of
     the column matrix [N,OH,OW,k*k*C] with ``weights.reshape(1,1,k*k*C,Cout)``,
     whose epilogue, dgrad and wgrad are Conv2D's (_ConvMFMAFn): the FrozenBN
-    fold, the fused ReLU with its ``_d2mi_relu_info`` tag, ``residual`` and
+    fold, the fused ReLU with its tag (handoff.ReluTag), ``residual`` and
     ``final_relu`` work as there.
 
     The offset conv runs on the MFMA conv too (rate 1): its 2*G*k*k = 18
@@ -812,7 +693,7 @@ class DeformConv2D(Conv2D):
         if self._offset_packed is None or self._offset_packed_key != key:
             self._offset_packed = ops.pack_conv_weights(w.detach())
             self._offset_packed_key = key
-        return _ConvMFMAFn.apply(x, w, b, self._offset_packed, self.stride, pads, False, None)
+        return _conv_mfma(x, w, b, self._offset_packed, self.stride, pads, relu=False)
 
     def call(self, inputs, residual=None, final_relu=False, res_grad_to=None, raw=False):
         """residual / final_relu / res_grad_to / raw: as Conv2D.call.  The input
@@ -839,8 +720,9 @@ class DeformConv2D(Conv2D):
                 self._cols_packed_key = key
             packed = self._cols_packed
         fuse_relu = norm is None and (is_relu(self.act_fn) or final_relu)
-        ret = _ConvMFMAFn.apply(cols, w1, b, packed, 1, (0, 0), fuse_relu, None, residual,
-                                bool(final_relu), False, res_grad_to)
+        links = handoff.Links(res_grad_to=res_grad_to) if res_grad_to is not None else None
+        ret = _conv_mfma(cols, w1, b, packed, 1, (0, 0), fuse_relu, residual=residual,
+                         relu_after=bool(final_relu), links=links)
         if raw:
             return ret
         if norm is not None:
@@ -906,8 +788,9 @@ class ConvTranspose2D(Layer):
             wp = self.weights.reshape(1, 1, k * k * self.out_channels, self.in_channels)
             b = self.bias.repeat(k * k) if self.bias is not None else None
             fuse = self.normalizer_fn is None and is_relu(self.act_fn)
-            y = _ConvMFMAFn.apply(inputs, wp.permute(0, 1, 3, 2), b, wp.detach().contiguous(), 1,
-                                  (0, 0), fuse, None, None, False, bool(relu_input_sole_consumer))
+            links = handoff.Links(sole_consumer=True) if relu_input_sole_consumer else None
+            y = _conv_mfma(inputs, wp.permute(0, 1, 3, 2), b, wp.detach().contiguous(), 1, (0, 0),
+                           fuse, links=links)
             y = y.reshape(N, H, W, k, k, self.out_channels).permute(0, 1, 3, 2, 4, 5)
             ret = y.reshape(N, H * k, W * k, self.out_channels)
             if self.normalizer_fn is not None:

@@ -176,10 +176,10 @@ class _RoIAlignFn(torch.autograd.Function):
     """ROIAlign forward/backward over 1..8 feature levels.  Boxes carry no
     gradient (crop_and_resize stop_gradient, lib/layers/functional.py:120).
 
-    grad_share (a dict shared by two poolings of the SAME feature maps, the
-    box and mask poolers of a training step, both of whose backwards always
-    run): the first backward writes the full maps and leaves them in the
-    dict, returning no gradient for the features; the second adds its
+    grad_share (a handoff.PoolerShare of two poolings of the SAME feature maps,
+    the box and mask poolers of a training step, both of whose backwards always
+    run): the first backward writes the full maps and leaves them there,
+    returning no gradient for the features; the second adds its
     contributions into them (d2mi_roi_align_bwd_ex accumulate: no second
     183 MB clear at 1333x800, no autograd add of two maps) and returns the
     sum — bit-identical to autograd's add of the two maps."""
@@ -223,8 +223,8 @@ class _RoIAlignFn(torch.autograd.Function):
         ctx.share = grad_share
         ctx.shapes = [f.shape for f in feats]
         # per-level input-gradient hand-off with another consumer of the same
-        # maps (the RPN head conv: ops / convolutional pair_grad protocol)
-        ctx.pairs = [getattr(f, "_d2mi_grad_pair", None) for f in feats]
+        # maps (the RPN head conv: a handoff.Pair per level)
+        ctx.pairs = [handoff.tagged(f, handoff.LEVEL_PAIR) for f in feats]
         ctx.save_for_backward(boxes, box_ind)
         ctx.set_materialize_grads(False)  # level (non-differentiable): no zero grad
         if level is not None:
@@ -244,16 +244,16 @@ class _RoIAlignFn(torch.autograd.Function):
             # leaves its grad_out; the second runs ONE backward over both ROI
             # sets (one emit per set, one sort, one gather pass summing each
             # set's run apart, set 0 + set 1)
-            first = share.pop("set0", None)
+            first = share.rois.take()
             g = _f32c(grad_out)
             if first is None:
-                handoff.deposit(share, "set0", (boxes, box_ind, g, ctx.params), "box/mask poolers")
+                share.rois.put((boxes, box_ind, g, ctx.params))
                 return (None,) * (4 + len(ctx.shapes))
             # levels whose other consumer already left its input gradient:
             # accumulate into it; the others: their pixel pass is deferred
             # into that consumer's backward, which writes the level's full
             # map (DEFER_PIXELS), or the map is written here and left for it
-            given = [pr.pop("g", None) if pr is not None else None for pr in ctx.pairs]
+            given = [pr.take() if pr is not None else None for pr in ctx.pairs]
             defer = [DEFER_PIXELS and pr is not None and gv is None
                      for pr, gv in zip(ctx.pairs, given)]
             grads = _roi_align_bwd2(first, (boxes, box_ind, g, ctx.params), ctx.shapes, given,
@@ -263,12 +263,12 @@ class _RoIAlignFn(torch.autograd.Function):
                 if pr is not None and gv is None:
                     # the other consumer adds it: a deferred pixel pass into its
                     # dgrad, or the map in its dgrad epilogue
-                    handoff.deposit(pr, "g", gr, "RPN head / ROI pooler level")
+                    pr.deposit(gr, "RPN head / ROI pooler level")
                     out.append(None)
                 else:
                     out.append(gr)
             return (None, None, None, None, *out)
-        prior = share.pop("maps", None) if share is not None else None
+        prior = share.maps.take() if share is not None else None
         if prior is not None:  # second of a pair: add into the first's maps
             grads = prior
         else:
@@ -296,7 +296,7 @@ class _RoIAlignFn(torch.autograd.Function):
                          extra=lambda: {"unique_bytes": R * out_h * out_w * C * 4 + maps})
         _C.check(rc, "d2mi_roi_align_bwd")
         if share is not None and prior is None:  # first of a pair: hand the maps over
-            handoff.deposit(share, "maps", grads, "box/mask poolers")
+            share.maps.put(grads)
             return (None,) * (4 + len(grads))
         return (None, None, None, None, *grads)
 
@@ -314,29 +314,7 @@ MERGED_BWD = True
 DEFER_PIXELS = True
 
 
-class DeferredPixels:
-    """The pixel pass of ONE level of a merged ROIAlign backward
-    (d2mi_roi_align_bwd2_ex phase 2), deposited for the backward that writes
-    that level's full gradient map.  add_into(gx) adds the pooled
-    contributions into gx in place (old + new at each touched pixel: the
-    rounding of autograd's sum of the two maps); materialize() returns the
-    pooled map alone (a fresh zeroed map + the pass), for a consumer that
-    cannot take it afterwards."""
-
-    def __init__(self, run, level, shape, device):
-        self._run, self.level, self.shape, self.device = run, level, tuple(shape), device
-
-    def add_into(self, gx):
-        if (tuple(gx.shape) != self.shape or gx.dtype != torch.float32 or not gx.is_contiguous()
-                or gx.device != self.device):
-            raise ValueError(f"deferred ROIAlign pixels: need a contiguous f32 {self.shape} map")
-        self._run(self.level, gx, True)
-        return gx
-
-    def materialize(self):
-        m = torch.empty(self.shape, dtype=torch.float32, device=self.device)
-        self._run(self.level, m, False)
-        return m
+DeferredPixels = handoff.DeferredPixels  # (one level's pixel pass, handed to its consumer)
 
 
 def _roi_align_bwd2(set0, set1, shapes, given=None, defer=None):

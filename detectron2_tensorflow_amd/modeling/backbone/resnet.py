@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 from ...layers import (BatchNorm, Conv2D, DeformConv2D, Layer, ModulatedDeformConv2D, get_norm,
                        ops)
+from ...layers import handoff
 from ...layers.activation import is_relu
 from ...layers import initializers as init
 from ...utils.arg_scope import add_arg_scope, arg_scope
@@ -63,12 +64,12 @@ class BottleneckBlock(Layer):
     def call(self, x):
         # projection shortcut: it and conv1 both read x; their input gradients
         # meet in the second one's epilogue instead of an autograd add
-        pair = ({} if self.grad_pair and self.shortcut is not None and torch.is_grad_enabled()
+        pair = (handoff.Pair() if self.grad_pair and self.shortcut is not None and torch.is_grad_enabled()
                 else None)
         if pair is not None:
             # a later reader of x (the FPN lateral) may join the pair: see
-            # layers/convolutional.py:_join_backward
-            x._d2mi_pair = pair
+            # layers/handoff.py
+            handoff.tag(x, handoff.STAGE_PAIR, pair)
         sc = self.shortcut(x, pair_grad=pair) if self.shortcut is not None else x
         # relu(conv3(...) + shortcut) in one kernel.  conv1 -> conv2 -> conv3 is
         # a chain of sole consumers: each one's dgrad applies the previous
@@ -77,7 +78,7 @@ class BottleneckBlock(Layer):
         # it before applying the mask of x (the previous block's ReLU output,
         # read by nothing else inside a stage): conv1 then carries x's whole
         # gradient -- no autograd add, no separate ReLU backward.
-        link = ({} if self.grad_handoff and self.shortcut is None and torch.is_grad_enabled()
+        link = (handoff.Slot() if self.grad_handoff and self.shortcut is None and torch.is_grad_enabled()
                 else None)
         h = self.conv1(x, relu_input_sole_consumer=link is not None, grad_from=link, pair_grad=pair)
         h = self.conv2(h, relu_input_sole_consumer=True)
@@ -116,12 +117,12 @@ class DeformBottleneckBlock(Layer):
         # sampler), so conv2 is not declared its sole consumer: conv1 applies
         # its own ReLU backward to autograd's sum of the two gradients.  conv3
         # is still the sole consumer of conv2's ReLU output.
-        pair = ({} if self.grad_pair and self.shortcut is not None and torch.is_grad_enabled()
+        pair = (handoff.Pair() if self.grad_pair and self.shortcut is not None and torch.is_grad_enabled()
                 else None)
         if pair is not None:
-            x._d2mi_pair = pair
+            handoff.tag(x, handoff.STAGE_PAIR, pair)
         sc = self.shortcut(x, pair_grad=pair) if self.shortcut is not None else x
-        link = ({} if self.grad_handoff and self.shortcut is None and torch.is_grad_enabled()
+        link = (handoff.Slot() if self.grad_handoff and self.shortcut is None and torch.is_grad_enabled()
                 else None)
         h = self.conv1(x, relu_input_sole_consumer=link is not None, grad_from=link, pair_grad=pair)
         h = self.conv2(h)

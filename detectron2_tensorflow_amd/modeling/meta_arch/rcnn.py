@@ -67,13 +67,13 @@ class GeneralizedRCNN(_Preprocess, Layer):
 
     def _tag_shared_levels(self, features):
         """FPN levels read by both the RPN head conv and the ROI poolers get a
-        gradient hand-off dict (the pair_grad protocol): whichever backward
+        gradient hand-off (a handoff.Pair): whichever backward
         runs first leaves its input gradient there and the other adds into it
         (the RPN dgrad epilogue, or the merged ROIAlign backward accumulating
         at touched pixels) -- no autograd add of two full maps, no zero-fill
         of the pooled levels.  Only when the ROI heads take the merged
         backward (box + mask poolers), which always consumes the hand-off."""
-        from ...layers import ops
+        from ...layers import handoff, ops
         rh, pg = self.roi_heads, self.proposal_generator
         if (pg is None or not getattr(rh, "mask_on", False) or not ops.MERGED_BWD
                 or not hasattr(pg, "rpn_head")):
@@ -82,7 +82,7 @@ class GeneralizedRCNN(_Preprocess, Layer):
         for f in shared:
             t = features[f]
             if t.is_cuda and t.requires_grad and t.shape[-1] >= 64:
-                t._d2mi_grad_pair = {}
+                handoff.tag(t, handoff.LEVEL_PAIR, handoff.Pair())
 
     def call(self, batched_inputs):
         if not self.training:

@@ -12,7 +12,7 @@ import os
 
 import torch
 
-from ...layers import Conv2D, Layer, ShapeSpec, get_norm, subsample, upsample
+from ...layers import Conv2D, Layer, ShapeSpec, get_norm, handoff, subsample, upsample
 from ...layers import initializers as init
 from ...utils.arg_scope import arg_scope
 from .build import NECK_REGISTRY
@@ -99,7 +99,7 @@ class FPN(Layer):
     # conv1 / projection-shortcut pair) and read by nothing else: the lateral
     # joins that pair's gradient hand-off, so the last of the three backwards
     # forms the feature's whole gradient with its ReLU mask (no autograd add,
-    # no threshold pass; layers/convolutional.py:_join_backward).
+    # no threshold pass; the join of layers/handoff.py).
     JOIN_GRAD = os.environ.get("D2MI_FPN_JOIN", "1") != "0"
 
     def _join_of(self, name, feats):
@@ -107,20 +107,20 @@ class FPN(Layer):
             return None
         if self.top_block is not None and getattr(self.top_block, "in_feature", None) == name:
             return None  # a third reader (P6 from C5)
-        return getattr(feats, "_d2mi_pair", None)
+        return handoff.tagged(feats, handoff.STAGE_PAIR)
 
     # A merged map read by its output conv and, as the top-down input, by the
     # next finer lateral: the two backwards hand its gradient over (the second
     # adds it; the output conv inside its dgrad epilogue) instead of an
-    # autograd add of two full maps (layers/convolutional.py ctx.td_pair).
+    # autograd add of two full maps (the top-down Pair of layers/handoff.py).
     TD_HANDOFF = os.environ.get("D2MI_FPN_TD", "1") != "0"
 
     def _out(self, out, prev, fused):
         if not (fused and self.TD_HANDOFF and torch.is_grad_enabled() and prev.requires_grad):
             return out(prev)
-        td = {"td": True}
+        td = handoff.Pair(topdown=True)
         y = out(prev, pair_grad=td)
-        prev._d2mi_td_pair = td  # (read by the finer lateral's forward)
+        handoff.tag(prev, handoff.TD_PAIR, td)  # (read by the finer lateral's forward)
         return y
 
     def call(self, bottom_up_features):

@@ -92,15 +92,15 @@ class StandardRPNHead(Layer):
         # the fused 1x1's weight / bias gradient accumulates over the levels in
         # one buffer (each level's skinny wgrad adds into it; the last level
         # returns the sum): autograd's per-level adds and slices go away
-        wacc = ({"n": len(features), "k": 0}
+        wacc = (handoff.LevelAccumulator(len(features), "RPN head 1x1 weight-gradient levels")
                 if fuse and torch.is_grad_enabled() and _RPNHead1x1Fn.ACC_LEVELS else None)
-        cacc = ({"n": len(features), "k": 0}
+        cacc = (handoff.LevelAccumulator(len(features), "shared conv weight-gradient calls")
                 if fuse and torch.is_grad_enabled() and StandardRPNHead.ACC_CONV_LEVELS else None)
         ys = []
-        pairs = [getattr(x, "_d2mi_grad_pair", None) for x in features]
+        pairs = [handoff.tagged(x, handoff.LEVEL_PAIR) for x in features]
         for li, x in enumerate(features):
             # a level the ROI poolers also read hands its input gradient over
-            # (GeneralizedRCNN tags them; the pair_grad protocol)
+            # (GeneralizedRCNN tags them with a handoff.Pair)
             share = self.conv(x, pair_grad=pairs[li], wacc=cacc)
             if fuse:
                 # the fused 1x1 is the declared SOLE consumer of the 3x3's ReLU
@@ -178,7 +178,7 @@ class _RPNHead1x1Fn(torch.autograd.Function):
     sole-consumer protocol of layers/convolutional.py:_ConvMFMAFn)."""
     GATE = True  # False: leave the ReLU backward to the 3x3 conv (tests)
     # True: the levels of one forward share a weight-gradient accumulator
-    # (wacc: {"n": levels, "k": done}); every level but the last returns no
+    # (wacc: a handoff.LevelAccumulator); every level but the last returns no
     # weight gradient, the last one the in-order sum -- autograd's
     # ((g1 + g2) + g3) ... of the per-level gradients, without its adds
     ACC_LEVELS = True
@@ -191,7 +191,7 @@ class _RPNHead1x1Fn(torch.autograd.Function):
         y = ops.conv2d_nhwc(share, wp, b16)
         A, D = wo.shape[3], wd.shape[3]
         ctx.save_for_backward(share, w16)
-        ctx.relu_info = getattr(share, "_d2mi_relu_info", None) if _RPNHead1x1Fn.GATE else None
+        ctx.relu_tag = handoff.tagged(share, handoff.RELU) if _RPNHead1x1Fn.GATE else None
         ctx.set_materialize_grads(False)  # a missing gradient is a zero one below
         ctx.dims = (A, D, y.shape[-1])
         ctx.wacc = wacc
@@ -207,46 +207,34 @@ class _RPNHead1x1Fn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             # 1x1 stride-1 dgrad: the forward weights' HWIO [1, 1, C, 16] is
             # the packed layout of the transposed conv
-            info = ctx.relu_info
-            if info is not None and share.shape[-1] % 4 == 0:
+            tag = ctx.relu_tag
+            if tag is not None and share.shape[-1] % 4 == 0:
                 gx = ops.conv2d_nhwc(g16, w16, None, 1, (0, 0), relu_gate=share)
-                info["masked"] = True
+                tag.masked = True
             else:
                 gx = ops.conv2d_nhwc(g16, w16, None, 1, (0, 0))
         acc = ctx.wacc
-        if acc is not None:
-            acc["k"] += 1
-            if acc["k"] == 1:
-                # every level's backward must run in this pass: otherwise the
-                # weight gradient (returned by the last level) never leaves
-                # and a stale buffer would poison a later backward
-                handoff.expect_complete(acc, lambda a: a["k"] == 0,
-                                        lambda a: (a.pop("buf", None), a.pop("lv", None),
-                                                   a.__setitem__("k", 0)),
-                                        "RPN head 1x1 weight-gradient levels")
-            if _RPNHead1x1Fn.LEVELS_ONE_LAUNCH:
-                # the levels' (input, gradient) pairs in backward order, one
-                # multi-level skinny wgrad at the last (the same sums)
-                acc.setdefault("lv", []).append((share, g16))
-            else:
-                acc["buf"] = ops.wgrad_skinny(share, g16, with_bias=True,
-                                              accumulate_into=acc.get("buf"))
-            if acc["k"] < acc["n"]:
-                return gx, None, None, None, None, None, None, None, None
-            if _RPNHead1x1Fn.LEVELS_ONE_LAUNCH:
-                lv = acc.pop("lv")
-                if len(lv) <= 8 and all(ops.skinny_levels_ok(x) for x, _ in lv):
-                    gw, gb = ops.wgrad_skinny_levels([x for x, _ in lv], [g for _, g in lv])
-                else:
-                    buf = None
-                    for x, g in lv:
-                        buf = ops.wgrad_skinny(x, g, with_bias=True, accumulate_into=buf)
-                    gw, gb = buf
-            else:
-                gw, gb = acc.pop("buf")
-            acc["k"] = 0  # (a second backward of the same graph starts over)
-        else:
+        if acc is None:
             gw, gb = ops.wgrad_skinny(share, g16, with_bias=True)
+        elif _RPNHead1x1Fn.LEVELS_ONE_LAUNCH:
+            # the levels' (input, gradient) pairs in backward order, one
+            # multi-level skinny wgrad at the last (the same sums)
+            lv = acc.defer((share, g16))
+            if lv is None:
+                return gx, None, None, None, None, None, None, None, None
+            if len(lv) <= 8 and all(ops.skinny_levels_ok(x) for x, _ in lv):
+                gw, gb = ops.wgrad_skinny_levels([x for x, _ in lv], [g for _, g in lv])
+            else:
+                buf = None
+                for x, g in lv:
+                    buf = ops.wgrad_skinny(x, g, with_bias=True, accumulate_into=buf)
+                gw, gb = buf
+        else:
+            out = acc.accumulate(lambda buf: ops.wgrad_skinny(share, g16, with_bias=True,
+                                                              accumulate_into=buf))
+            if out is None:
+                return gx, None, None, None, None, None, None, None, None
+            gw, gb = out
         return (gx, gw[..., :A].contiguous(), gb[:A], gw[..., A:A + D].contiguous(), gb[A:A + D],
                 None, None, None, None)
 

@@ -9,7 +9,7 @@ values the reference's SparseBoxList.to_dense produces.
 """
 import torch
 
-from ...layers import ShapeSpec, ops
+from ...layers import ShapeSpec, handoff, ops
 from ...structures import BoxList
 from ...utils import capture, host_sync
 from ...utils.registry import Registry
@@ -220,7 +220,7 @@ class StandardROIHeads(ROIHeads):
             sampled = self.label_and_sample_proposals(proposals, targets)
             # the box and mask poolers read the same p2..p5: one gradient map
             # set for both backwards (ops._RoIAlignFn grad_share)
-            share = {} if self.mask_on else None
+            share = handoff.PoolerShare() if self.mask_on else None
             # the mask branch's foreground count is read while the box branch
             # is enqueued (the device never idles at the read)
             pending = None

@@ -1162,6 +1162,7 @@ def test_relu_gate_fused_into_consumer_dgrad(dev, declared):
     consumer of a fused-ReLU output applies that ReLU's backward in its own
     dgrad epilogue (kMaskByResidual) and the producer skips its own; without
     the declaration nothing is fused.  Gradients match float64 autograd."""
+    from detectron2_tensorflow_amd.layers import handoff
     from detectron2_tensorflow_amd.layers.convolutional import _ConvMFMAFn
     g = torch.Generator().manual_seed(11)
     x = torch.randn(2, 12, 15, 64, generator=g)
@@ -1185,11 +1186,12 @@ def test_relu_gate_fused_into_consumer_dgrad(dev, declared):
     for i in range(3):
         w, b = dx[1 + i], dx[4 + i]
         h = _ConvMFMAFn.apply(h, w, b, ops().pack_conv_weights(w.detach()), 1, (1, 1), i < 2,
-                              None, None, False, declared and i > 0)
+                              None, None, False,
+                              handoff.Links(sole_consumer=True) if declared and i > 0 else None)
         outs.append(h)
     h.backward(gy.to(dev))
-    assert outs[0]._d2mi_relu_info["masked"] is declared
-    assert outs[1]._d2mi_relu_info["masked"] is declared
+    assert handoff.tagged(outs[0], handoff.RELU).masked is declared
+    assert handoff.tagged(outs[1], handoff.RELU).masked is declared
     for name, a, r in zip(["x", "w0", "w1", "w2", "b0", "b1", "b2"], dx, lx):
         np.testing.assert_allclose(a.grad.cpu().double().numpy(), r.grad.numpy(), rtol=1e-4,
                                    atol=2e-4 * max(1.0, float(r.grad.abs().max())), err_msg=name)
@@ -1342,7 +1344,7 @@ def test_stage_output_join_with_fpn_lateral_is_exact(dev, lateral_first):
     gradients of the autograd formulation (adds + threshold_backward).  The
     lateral created first runs its backward last (autograd runs ready nodes
     by creation order, newest first): both completion orders are exercised."""
-    from detectron2_tensorflow_amd.layers import Conv2D
+    from detectron2_tensorflow_amd.layers import Conv2D, handoff
     torch.manual_seed(5)
     prod = Conv2D(64, 128, 3, activation="relu", impl="mfma", scope="prod").to(dev)
     conv1 = Conv2D(128, 32, 1, stride=2, impl="mfma", scope="conv1").to(dev)
@@ -1361,7 +1363,7 @@ def test_stage_output_join_with_fpn_lateral_is_exact(dev, lateral_first):
             m.zero_grad(set_to_none=True)
         xi = x.clone().requires_grad_(True)
         c = prod(xi)
-        pair = {}
+        pair = handoff.Pair()
         if lateral_first:
             lo = lat(c, topdown=td, join=pair if join else None)
         sc = short(c, pair_grad=pair)
@@ -1370,8 +1372,8 @@ def test_stage_output_join_with_fpn_lateral_is_exact(dev, lateral_first):
             lo = lat(c, topdown=td, join=pair if join else None)
         torch.autograd.backward([h, sc, lo], [gh, gs, gl])
         if join:
-            assert pair.get("last") == ("lateral" if lateral_first else "pair")
-            assert not ({"g", "sum", "lat"} & pair.keys())  # nothing left behind
+            assert pair.completed_by == ("lateral" if lateral_first else "pair")
+            assert pair.empty  # nothing left behind
         res[join] = (xi.grad, {n: q.grad.clone() for m in mods for n, q in m.named_parameters()})
     gxa, gpa = res[True]
     gxb, gpb = res[False]
@@ -1512,6 +1514,7 @@ def test_roi_align_backward_grad_share_matches_autograd_sum(dev, merged):
 
 
 def _grad_share_case(dev):
+    from detectron2_tensorflow_amd.layers.handoff import PoolerShare
     rng = np.random.default_rng(45)
     N, IH, IW, C = 2, 256, 320, 64
     strides = [4, 8, 16, 32]
@@ -1523,7 +1526,7 @@ def _grad_share_case(dev):
     g1 = torch.from_numpy(rng.normal(size=(400, 7, 7, C)).astype(F32)).to(dev)
     g2 = torch.from_numpy(rng.normal(size=(64, 14, 14, C)).astype(F32)).to(dev)
     grads = []
-    for share in (None, {}):
+    for share in (None, PoolerShare()):
         xs = [torch.from_numpy(f).to(dev).requires_grad_(True) for f in feats]
         o1 = ops().roi_align(xs, torch.from_numpy(b1).to(dev), torch.from_numpy(i1).to(dev), (7, 7),
                              scales, 0, True, grad_share=share)
@@ -1531,7 +1534,7 @@ def _grad_share_case(dev):
                              (14, 14), scales, 0, True, grad_share=share)
         torch.autograd.backward([o1, o2], [g1, g2])
         grads.append([x.grad.clone() for x in xs])
-        assert share is None or not share  # the second backward took the maps
+        assert share is None or share.empty  # the second backward took the maps
     for a, b in zip(*grads):
         assert torch.equal(a, b)
 

@@ -571,7 +571,7 @@ def test_fpn_join_engages_and_matches_plain_step(dev, monkeypatch):
     C3 and C4 (the next stage's conv1 / shortcut pair + the FPN lateral: three
     members each; C2 is frozen) and the step's gradients equal those with the
     join off (FPN.JOIN_GRAD = False: autograd add + threshold_backward)."""
-    from detectron2_tensorflow_amd.layers import convolutional as conv_mod
+    from detectron2_tensorflow_amd.layers import handoff
     from detectron2_tensorflow_amd.modeling import build_model
     from detectron2_tensorflow_amd.modeling.necks.fpn import FPN
     from detectron2_tensorflow_amd.utils.synthetic import (calibrate_rcnn_scores,
@@ -582,13 +582,13 @@ def test_fpn_join_engages_and_matches_plain_step(dev, monkeypatch):
     batch = synthetic_train_batch(2, 256, 320, 5, dev)
     calibrate_rcnn_scores(model, batch)
     calls = []
-    real = conv_mod._join_backward
 
-    def counted(ctx, *args):
-        calls.append("lateral" if ctx.join is not None else "pair")
-        return real(ctx, *args)
+    def observe(label, event):
+        # every arrival at a join deposits or completes it, exactly one of the two
+        if label.startswith("join (") and event in ("deposit", "complete"):
+            calls.append("lateral" if label == "join (lateral)" else "pair")
 
-    monkeypatch.setattr(conv_mod, "_join_backward", counted)
+    monkeypatch.setattr(handoff, "OBSERVER", observe)
     # (no MIOpen conv on this path since the r3 MFMA stem; the flag keeps a
     # torch fallback conv -- strided 3x3 dgrad, grouped / dilated -- exact too)
     monkeypatch.setattr(torch.backends.cudnn, "deterministic", True)
@@ -616,7 +616,7 @@ def test_fpn_topdown_handoff_engages_and_matches_plain_step(dev, monkeypatch):
     backwards hand the gradient over (the output conv adds it in its dgrad
     epilogue) -- engaged at three levels, and the step's gradients equal those
     of the autograd add (TD_HANDOFF False), bit for bit."""
-    from detectron2_tensorflow_amd.layers import convolutional as conv_mod
+    from detectron2_tensorflow_amd.layers import handoff
     from detectron2_tensorflow_amd.modeling import build_model
     from detectron2_tensorflow_amd.modeling.necks.fpn import FPN
     from detectron2_tensorflow_amd.utils.synthetic import (calibrate_rcnn_scores,
@@ -627,13 +627,8 @@ def test_fpn_topdown_handoff_engages_and_matches_plain_step(dev, monkeypatch):
     batch = synthetic_train_batch(2, 256, 320, 5, dev)
     calibrate_rcnn_scores(model, batch)
     deposits = []
-    real = conv_mod.handoff.deposit
-
-    def counted(d, key, value, what):
-        deposits.append(what)
-        return real(d, key, value, what)
-
-    monkeypatch.setattr(conv_mod.handoff, "deposit", counted)
+    monkeypatch.setattr(handoff, "OBSERVER",
+                        lambda label, event: event == "deposit" and deposits.append(label))
     monkeypatch.setattr(torch.backends.cudnn, "deterministic", True)
     grads = {}
     for td in (True, False):
@@ -697,7 +692,7 @@ def test_deferred_roi_pixel_passes_are_exact(dev, monkeypatch):
     a second full map.  Every level is deferred in a training step, and the
     model's gradients equal the full-map hand-off's bit for bit (old + new at
     each touched pixel is the same rounding as dgrad + pooled map)."""
-    from detectron2_tensorflow_amd.layers import ops
+    from detectron2_tensorflow_amd.layers import handoff, ops
     from detectron2_tensorflow_amd.modeling import build_model
     from detectron2_tensorflow_amd.utils.synthetic import (calibrate_rcnn_scores,
                                                            synthetic_train_batch)
@@ -708,13 +703,12 @@ def test_deferred_roi_pixel_passes_are_exact(dev, monkeypatch):
     calibrate_rcnn_scores(model, batch)
     monkeypatch.setattr(torch.backends.cudnn, "deterministic", True)
     applied = []
-    real = ops.DeferredPixels.add_into
 
-    def counted(self, gx):
-        applied.append(self.level)
-        return real(self, gx)
+    def observe(label, event):
+        if label == "deferred pixels":  # "apply level <l>"
+            applied.append(int(event.rsplit(" ", 1)[1]))
 
-    monkeypatch.setattr(ops.DeferredPixels, "add_into", counted)
+    monkeypatch.setattr(handoff, "OBSERVER", observe)
     grads = {}
     for defer in (True, False):
         monkeypatch.setattr(ops, "DEFER_PIXELS", defer)
