@@ -2,11 +2,12 @@
 
 Key names and default values follow the reference's lib/config/defaults.py
 (:17-785) for every subtree the detection path reads (MODEL.* for
-GeneralizedRCNN / SingleStageDetector / ResNet / FPN / RPN / ROI heads /
-RetinaNet / SOLO inference, SOLVER, TRANSFORM, TEST, ...), so the reference
-YAML files merge without unknown-key errors.  Subsystems this build does not
-implement (SpineNet, YOLOv4, panoptic, data augmentation, TFRecord readers)
-keep only the keys the shipped YAMLs set.
+GeneralizedRCNN / SingleStageDetector / PanopticFPN / SemanticSegmentor /
+ResNet / FPN / RPN / ROI heads / RetinaNet / SOLO / the semantic head, SOLVER,
+TRANSFORM, TEST, ...), so the reference YAML files merge without unknown-key
+errors.  Subsystems this build does not implement (SpineNet, YOLOv4, the
+panoptic evaluator, data augmentation, TFRecord readers) keep only the keys
+the shipped YAMLs set.
 """
 from .config import CfgNode
 
@@ -62,6 +63,10 @@ def _tree():
         "SEM_SEG_HEAD": {"NAME": "SemSegFPNHead", "IN_FEATURES": ["p2", "p3", "p4", "p5"],
                          "IGNORE_VALUE": -1, "NUM_CLASSES": 54, "CONVS_DIM": 128,
                          "COMMON_STRIDE": 4, "NORM": "GN", "LOSS_WEIGHT": 1.0},
+        "PANOPTIC_FPN": {"INSTANCE_LOSS_WEIGHT": 1.0,
+                         "COMBINE": {"ENABLED": True, "OVERLAP_THRESH": 0.5,
+                                     "STUFF_AREA_LIMIT": 4096,
+                                     "INSTANCES_CONFIDENCE_THRESH": 0.5}},
         "SINGLE_STAGE_HEAD": {"NAME": "RetinaNetHead", "NUM_CLASSES": 80,
                               "IN_FEATURES": ["p3", "p4", "p5", "p6", "p7"],
                               "IOU_THRESHOLDS": [0.4, 0.5], "IOU_LABELS": [0, -1, 1]},

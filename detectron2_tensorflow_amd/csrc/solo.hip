@@ -36,38 +36,13 @@
 
 #include "common.h"
 #include "internal.h"
+#include "resize.h"
 
 namespace d2mi {
 namespace {
 
 // ------------------------------------------------------------ ResizeBilinear
-// TF 1.15 resize_bilinear_op.cc: compute_interpolation_weights with
-// HalfPixelScaler ((x + 0.5) * scale - 0.5) or LegacyScaler (x * scale);
-// lower = max(floor(in), 0), upper = min(ceil(in), in_size - 1),
-// lerp = in - floor(in); compute_lerp: top = tl + (tr - tl) * xl,
-// bottom = bl + (br - bl) * xl, out = top + (bottom - top) * yl.
-struct Interp {
-  int lo, hi;
-  float lerp;
-};
-
-__device__ __forceinline__ Interp interp_at(int i, float scale, int in_size, int half_pixel) {
-  const float in = half_pixel ? ((float)i + 0.5f) * scale - 0.5f : (float)i * scale;
-  const float in_f = floorf(in);
-  Interp r;
-  r.lo = max((int)in_f, 0);
-  r.hi = min((int)ceilf(in), in_size - 1);
-  r.lerp = in - in_f;
-  return r;
-}
-
-__device__ __forceinline__ float tf_lerp(float tl, float tr, float bl, float br, float xl,
-                                         float yl) {
-  const float top = tl + (tr - tl) * xl;
-  const float bottom = bl + (br - bl) * xl;
-  return top + (bottom - top) * yl;
-}
-
+// (the TF 1.15 interpolation arithmetic: resize.h)
 template <bool VEC4>
 __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __restrict__ x,
                                                               float* __restrict__ y, int N, int H,
@@ -102,12 +77,6 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __res
       y[e] = tf_lerp(b[tl + cv], b[tr + cv], b[bl + cv], b[br + cv], ix.lerp, iy.lerp);
     }
   }
-}
-
-// CalculateResizeScale (TF image_resizer_state.h), float division.
-static float resize_scale(int in, int out, int align_corners) {
-  return (align_corners && out > 1) ? (float)(in - 1) / (float)(out - 1)
-                                    : (float)in / (float)out;
 }
 
 __device__ __forceinline__ float sigmoidf_tf(float v) { return 1.f / (1.f + expf(-v)); }

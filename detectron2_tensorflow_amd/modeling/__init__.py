@@ -2,7 +2,9 @@
 from .anchor_generator import ANCHOR_GENERATOR_REGISTRY, DefaultAnchorGenerator, build_anchor_generator
 from .backbone import BACKBONE_REGISTRY, build_backbone
 from .box_regression import Box2BoxTransform
-from .meta_arch import META_ARCH_REGISTRY, GeneralizedRCNN, ProposalNetwork, SingleStageDetector, build_model
+from .meta_arch import (META_ARCH_REGISTRY, SEM_SEG_HEADS_REGISTRY, GeneralizedRCNN, PanopticFPN,
+                        ProposalNetwork, SemanticSegmentor, SemSegFPNHead, SingleStageDetector,
+                        build_model, build_sem_seg_head)
 from .necks import FPN, NECK_REGISTRY, build_neck
 from .poolers import ROIPooler, assign_boxes_to_levels
 from .proposal_generator import PROPOSAL_GENERATOR_REGISTRY, RPN, RPN_HEAD_REGISTRY

@@ -1000,6 +1000,68 @@ int d2mi_deform_sample_bwd(const float* x, const float* offsets, const float* gc
                            int off_stride, int goff_stride, float* gx, float* goffsets, void* ws,
                            size_t ws_bytes, void* stream);
 
+/* ------------------------------------- semantic segmentation / panoptic merge
+ * SemSegFPNHead's tail without a full-resolution tensor
+ * (lib/modeling/meta_arch/semantic_seg.py:197-218): resize_images(x, x scale)
+ * -- the half-pixel ResizeBilinear, d2mi_resize_bilinear's arithmetic -- then
+ * the mean over the not-ignored pixels of the sparse softmax cross-entropy,
+ * times loss_weight.  logits [N, h, w, ldc] f32 (channels 0..C-1 of every
+ * ldc-float row are the classes, C <= ldc); labels [N, Hl, Wl] int32 on the
+ * [h*scale, w*scale] output grid's coordinates; image_shapes [N, 2] int32
+ * true (h, w).  An output pixel counts unless its label equals ignore_value
+ * (or is no class: outside [0, C)), or it lies outside the image's true shape
+ * or the label extent (ImageList.from_tensors(..., pad_value=ignore_value),
+ * semantic_seg.py:68-73, without the padded copy).  loss[0] = loss_weight *
+ * sum / count, 0 when count[0] is 0.  Fixed-order sums (f64 accumulators,
+ * per-workgroup partials, one ordered final pass): bitwise reproducible.
+ * 1 <= scale <= 8; workspace from d2mi_sem_seg_loss_workspace_size. */
+size_t d2mi_sem_seg_loss_workspace_size(int N, int h, int w);
+int d2mi_sem_seg_loss_fwd(const float* logits, int N, int h, int w, int C, int ldc,
+                          const int32_t* labels, int Hl, int Wl, const int32_t* image_shapes,
+                          int ignore_value, int scale, float loss_weight, float* loss,
+                          int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+/* Gradient of the above w.r.t. logits (semantic_seg.py:197-218 through TF
+ * autodiff), as a gather: grad_logits [N, h, w, ldc], every element written
+ * (channels C..ldc-1 with 0), = grad_loss[0] * loss_weight / count[0] * the
+ * sum over the output pixels whose bilinear footprint touches the pixel of
+ * weight * (softmax - onehot), the softmax recomputed, summed in row-major
+ * order of the output pixels.  count: d2mi_sem_seg_loss_fwd's (device);
+ * grad_loss [1] f32 (device).  No atomics, bitwise reproducible. */
+int d2mi_sem_seg_loss_bwd(const float* logits, int N, int h, int w, int C, int ldc,
+                          const int32_t* labels, int Hl, int Wl, const int32_t* image_shapes,
+                          int ignore_value, int scale, float loss_weight, const int32_t* count,
+                          const float* grad_loss, float* grad_logits, void* stream);
+/* sem_seg_postprocess(..., "conventional") + tf.argmax
+ * (lib/modeling/postprocessing.py:62-95, lib/modeling/meta_arch/
+ * panoptic_fpn.py:118-131; the resize of semantic_seg.py:197-201 before
+ * them): out [N, h*scale, w*scale] int64 = the argmax over the C classes of
+ * the interpolated logits (lowest index on ties) inside image_shapes[n], 0
+ * outside (the argmax of the zero padding). */
+int d2mi_sem_seg_argmax(const float* logits, int N, int h, int w, int C, int ldc,
+                        const int32_t* image_shapes, int scale, int64_t* out, void* stream);
+/* combine_semantic_and_instance_outputs (panoptic_fpn.py:160-296), N images.
+ * masks [N, D, H, W] u8 (pasted, > 0 is set); scores [N, D] f32; classes
+ * [N, D] int64; boxes [N, D, 4] f32; is_valid [N, D] u8; sem_seg [N, H, W]
+ * int64.  Instances in descending score (ties: lower index); rank i has id
+ * i + 1 and is applied when valid, score > conf_thresh, area > 0 and
+ * (float)intersect / (float)area < overlap_thresh (integer pixel counts).
+ * Stuff label l in [1, num_stuff_classes) has id D + l and claims the
+ * still-empty pixels of its class when their count exceeds stuff_area_limit;
+ * its bbox is their [ymin, xmin, ymax, xmax] (inclusive), else zeros.
+ * panoptic_seg [N, H, W] int32; the seg_* arrays have D + num_stuff_classes
+ * - 1 rows per image (seg_bbox x 4).  D + 3 launches: one per instance
+ * (apply rank i from the device counters while counting rank i + 1, integer
+ * atomics), two for the stuff labels.  No host read. */
+size_t d2mi_panoptic_combine_workspace_size(int N, int D, int num_stuff_classes);
+int d2mi_panoptic_combine(const uint8_t* masks, const float* scores, const int64_t* classes,
+                          const float* boxes, const uint8_t* is_valid, const int64_t* sem_seg,
+                          int N, int D, int H, int W, float overlap_thresh,
+                          float stuff_area_limit, float conf_thresh, int num_stuff_classes,
+                          int32_t* panoptic_seg, int32_t* seg_id, uint8_t* seg_isthing,
+                          float* seg_score, int64_t* seg_category_id, int32_t* seg_instance_id,
+                          float* seg_bbox, uint8_t* seg_is_valid, float* seg_area,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
