@@ -170,7 +170,8 @@ def scratch(nbytes, device):
 
 
 _ERR_BITS = {1: "box index out of range", 2: "NMS candidate capacity exceeded",
-             4: "top-k candidate capacity exceeded"}
+             4: "top-k candidate capacity exceeded",
+             8: "declared bound on the non-zero gradient rows exceeded"}
 
 
 def error_word(device=None):

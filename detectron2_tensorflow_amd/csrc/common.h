@@ -40,6 +40,7 @@ enum ErrorBits : int32_t {
   kErrBoxInd = 1,
   kErrNmsCapacity = 2,
   kErrTopkCapacity = 4,
+  kErrRowBound = 8,  // a declared bound on the non-zero gradient rows was false (conv_rows.hip)
 };
 
 // float -> uint32 whose unsigned order equals the float order.  -0.0 maps to

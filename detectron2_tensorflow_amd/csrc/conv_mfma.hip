@@ -129,6 +129,12 @@ struct ConvArgs {
   int lv_H[kMaxConvLevels], lv_W[kMaxConvLevels], lv_OH[kMaxConvLevels], lv_OW[kMaxConvLevels];
   int lv_N[kMaxConvLevels], lv_xbytes[kMaxConvLevels], lv_tile0[kMaxConvLevels + 1];
   int lv_moff[kMaxConvLevels + 1];  // first row of each level in the split-K slab; [6] = total
+  // Row-list launch (d2mi_conv2d_nhwc_rows, conv_mfma_kernel<..., ROWS>): tile
+  // row r stands for output pixel rows[tile_m * BM + r], for the first *nrows
+  // entries (device side); split-K slabs are compact, rows_stride rows each.
+  const int32_t* rows;
+  const int32_t* nrows;
+  int rows_stride;
 };
 
 // The per-level part of a launch's arguments: a single-level launch takes
@@ -334,7 +340,9 @@ __device__ __forceinline__ void store_partial(const ConvArgs& a, const Geo& g,
 // loaded as float4s BEFORE its LDS barrier (their latency overlaps the
 // transpose).  Same arithmetic order as epilogue(); split-K partials are
 // written raw.  smem: >= 32 * (BN + 4) floats of the kernel's LDS.
-template <int WM, int WN, int TM, int TN, int NT = 256>
+// ROWS: tile row mi stands for output pixel a.rows[mi] (mi < g.M listed rows;
+// pixels from a.m_end up belong to the dense tail launch and are not written).
+template <int WM, int WN, int TM, int TN, int NT = 256, bool ROWS = false>
 __device__ __forceinline__ void store_outputs_lds(const ConvArgs& a, const Geo& g,
                                                   floatx16 (&acc)[TM][TN],
                                                   int m0, int n0, int wr, int wc, int lane,
@@ -356,9 +364,10 @@ __device__ __forceinline__ void store_outputs_lds(const ConvArgs& a, const Geo& 
     for (int q = 0; q < Q; ++q) {
       const int idx = tid + NT * q;
       const int row = idx / F4, c4 = idx - row * F4;
-      const int m = m0 + s * 32 + row, co = n0 + c4 * 4;
+      const int mi = m0 + s * 32 + row, co = n0 + c4 * 4;
+      const int m = ROWS ? (mi < g.M ? a.rows[mi] : a.m_end) : mi;
       res[q] = gt[q] = td[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (!part && m < g.M && co < a.Cout) {
+      if (!part && mi < g.M && (!ROWS || m < a.m_end) && co < a.Cout) {
         const size_t o = (size_t)m * a.Cout + co;
         if (a.residual) res[q] = ld4(a.residual + o);
         if (g.gate) gt[q] = ld4(g.gate + o);
@@ -383,8 +392,10 @@ __device__ __forceinline__ void store_outputs_lds(const ConvArgs& a, const Geo& 
     for (int q = 0; q < Q; ++q) {
       const int idx = tid + NT * q;
       const int row = idx / F4, c4 = idx - row * F4;
-      const int m = m0 + s * 32 + row, co = n0 + c4 * 4;
-      if (m >= g.M || co >= a.Cout) continue;
+      const int mi = m0 + s * 32 + row, co = n0 + c4 * 4;
+      if (mi >= g.M || co >= a.Cout) continue;
+      const int m = ROWS ? a.rows[mi] : mi;
+      if (ROWS && m >= a.m_end) continue;
       float4 v = *reinterpret_cast<const float4*>(&smem[row * LS + c4 * 4]);
       if (!part) {
         float* vv = reinterpret_cast<float*>(&v);
@@ -466,8 +477,10 @@ __device__ __forceinline__ int xcd_tile(int xcd2, int& split) {
   return xcd2 ? l - split * nx : l;
 }
 
-template <int WM, int WN, int TM, int TN, bool DB, bool SPLIT, int OCC = 2, bool ML = false>
+template <int WM, int WN, int TM, int TN, bool DB, bool SPLIT, int OCC = 2, bool ML = false,
+          bool ROWS = false>
 __global__ __launch_bounds__(256, OCC) void conv_mfma_kernel(ConvArgs a) {
+  static_assert(!(ROWS && ML), "a row list belongs to one level");
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr int RA = BM / 32, RB = BN / 32;  // staged rows per thread (8 threads per row)
   constexpr int NB = DB ? 2 : 1;
@@ -482,9 +495,16 @@ __global__ __launch_bounds__(256, OCC) void conv_mfma_kernel(ConvArgs a) {
   // and neighbouring pixel tiles, which share input halo rows) land on one XCD.
   int split;
   int tile = a.tile_base + xcd_tile(a.xcd2, split);
-  const Geo g = ML ? select_level(a, tile) : geo_of(a);  // ML: a multi-level launch
+  Geo g = ML ? select_level(a, tile) : geo_of(a);  // ML: a multi-level launch
   const int mt = tile / a.nN, nt = tile - mt * a.nN;
   const int m0 = mt * BM, n0 = nt * BN;
+  if constexpr (ROWS) {
+    // rows are list positions from here on: g.M bounds them, the slabs are compact
+    g.M = *a.nrows;
+    g.pstride = a.rows_stride;
+    g.prow0 = 0;
+    if (m0 >= g.M) return;  // (the grid is sized by the list's capacity)
+  }
   const int kt0 = split * a.kt_per_split;
   const int kt1 = min(a.nk, kt0 + a.kt_per_split);
 
@@ -503,7 +523,7 @@ __global__ __launch_bounds__(256, OCC) void conv_mfma_kernel(ConvArgs a) {
 #pragma unroll
   for (int p = 0; p < RA; ++p) {
     const int m = m0 + srow + 32 * p;
-    const int mm = m < g.M ? m : 0;
+    const int mm = m < g.M ? (ROWS ? a.rows[m] : m) : 0;
     const int n = mm / (g.OH * g.OW);
     const int rem = mm - n * g.OH * g.OW;
     const int oh = rem / g.OW, ow = rem - oh * g.OW;
@@ -726,7 +746,13 @@ __global__ __launch_bounds__(256, OCC) void conv_mfma_kernel(ConvArgs a) {
   // split-K partial slabs leave straight from the accumulators (each store
   // instruction writes two whole 128-B row segments; no LDS round trip and
   // none of its barriers) unless tuning conv_epi = 0
-  if (a.splits > 1 && a.reg_partials) {
+  if constexpr (ROWS) {
+    if (a.splits > 1)  // compact slab rows = list positions
+      store_outputs<WN, TM, TN>(a, g, acc, m0, n0, wr, wc, lane, split, true);
+    else
+      store_outputs_lds<WM, WN, TM, TN, 256, true>(a, g, acc, m0, n0, wr, wc, lane, split, false,
+                                                   &As[0][0]);
+  } else if (a.splits > 1 && a.reg_partials) {
     store_outputs<WN, TM, TN>(a, g, acc, m0, n0, wr, wc, lane, split, true);
   } else if (WN * TN * 32 == 128 || a.lds_epi)  // 128-wide tiles: planned only with lds_epi
     store_outputs_lds<WM, WN, TM, TN>(a, g, acc, m0, n0, wr, wc, lane, split, a.splits > 1,
@@ -1326,6 +1352,47 @@ __global__ void splitk_reduce4_kernel(ConvArgs a) {
   }
 }
 
+// Row-list launch: y rows [0, a.m_end) := epilogue(0) -- what the dense
+// kernel writes where every product is zero: 0.f (+ residual: an add, so a
+// -0.0 residual becomes +0.0 as there), zero where the gate is not positive.
+// A kernel, not a memset: a captured memset node is not ordered like a launch.
+__global__ void rows_fill_kernel(ConvArgs a) {
+  const Geo g = geo_of(a);
+  const int C4 = a.Cout >> 2;
+  const int64_t total4 = (int64_t)a.m_end * C4;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total4;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int m = (int)(i / C4), co = 4 * (int)(i - (int64_t)m * C4);
+    const float4 o = epilogue4(a, g, make_float4(0.f, 0.f, 0.f, 0.f), m, co);
+    *reinterpret_cast<float4*>(a.y + (size_t)m * a.Cout + co) = o;
+  }
+}
+
+// splitk_reduce4_kernel over the compact slabs of a row-list launch: the same
+// split order, the epilogue at the listed pixel.
+__global__ void rows_reduce4_kernel(ConvArgs a) {
+  const Geo g = geo_of(a);
+  const int C4 = a.Cout >> 2;
+  const int t4 = *a.nrows * C4;
+  const size_t slab4 = (size_t)a.rows_stride * C4;
+  const float4* p4 = reinterpret_cast<const float4*>(a.partial);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < t4; i += gridDim.x * blockDim.x) {
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 8
+    for (int s = 0; s < a.splits; ++s) {
+      const float4 v = p4[s * slab4 + i];
+      acc.x += v.x;
+      acc.y += v.y;
+      acc.z += v.z;
+      acc.w += v.w;
+    }
+    const int ml = i / C4, co = 4 * (i - ml * C4);
+    const int m = a.rows[ml];
+    if (m >= a.m_end) continue;  // (the dense tail launch writes those)
+    *reinterpret_cast<float4*>(a.y + (size_t)m * a.Cout + co) = epilogue4(a, g, acc, m, co);
+  }
+}
+
 // Multi-level split-K: rows of the concatenated slab -> (level, row), fixed
 // split order, + bias (+ ReLU); float4 over channels (Cout % 4 == 0).
 __global__ void splitk_reduce_levels_kernel(ConvArgs a) {
@@ -1625,13 +1692,26 @@ extern "C" int d2mi_conv2d_plan(int N, int H, int W, int Cin, int Cout, int KH, 
   return emit_plan(v, (int)(sizeof(v) / sizeof(v[0])), out, out_len);
 }
 
+// The dilated row list of a census (d2mi_conv2d_nhwc_rows): `cap` entries of
+// capacity (a multiple of 128), *nrows of them listed.
+struct RowList {
+  const int32_t* rows;
+  const int32_t* nrows;
+  int cap;
+};
+
 // Shared launcher of the f32-operand convs (the split or native-f32 MFMA
 // products, flags bit 2): fill ConvArgs from the plan, launch its kernels.
+// rl (d2mi_conv2d_nhwc_rows, which has checked that the plan allows it): the
+// main launch is replaced by a fill of its rows with epilogue(0) and a
+// 128x64-tile launch over the listed rows with the main launch's K splits
+// (bit-identical per element: the same k-step order, product order and split
+// boundaries as the plan's own kernel); the tail launch runs as planned.
 static int conv_core(const float* x, const float* w_packed, const float* bias,
                      const float* topdown, const float* residual, const float* gate, float* y,
                      int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
                      int pad_beg, int pad_end, int flags, void* workspace,
-                     size_t workspace_bytes, void* stream) {
+                     size_t workspace_bytes, void* stream, const RowList* rl = nullptr) {
   ConvPlan p;
   D2MI_REQUIRE(plan_conv({N, H, W, Cin, Cout, KH, KW, stride, pad_beg, pad_end}, flags,
                          plan_operands(topdown, residual, gate, y, bias, workspace),
@@ -1714,6 +1794,36 @@ static int conv_core(const float* x, const float* w_packed, const float* bias,
     D2MI_LAUNCH_CHECK();
     return 0;
   };
+  if (rl != nullptr) {
+    const ConvLaunch& l = p.main;
+    ConvArgs c = a;
+    c.m_base = 0;
+    c.m_end = l.m_end;
+    const int C4 = Cout / 4;
+    hipLaunchKernelGGL(rows_fill_kernel,
+                       dim3((unsigned)std::min<int64_t>(((int64_t)l.m_end * C4 + 255) / 256, 8192)),
+                       dim3(256), 0, st, c);
+    D2MI_LAUNCH_CHECK();
+    c.rows = rl->rows;
+    c.nrows = rl->nrows;
+    c.rows_stride = rl->cap;
+    c.nN = (Cout + 63) / 64;
+    c.tile_base = 0;
+    c.ntiles = rl->cap / 128 * c.nN;
+    c.splits = l.splits;
+    c.kt_per_split = l.kt_per_split;
+    c.partial = l.splits > 1 ? sp.main : nullptr;
+    hipLaunchKernelGGL((conv_mfma_kernel<4, 1, 1, 2, true, true, 2, false, true>),
+                       dim3(c.ntiles, l.splits), dim3(256), 0, st, c);
+    D2MI_LAUNCH_CHECK();
+    if (l.splits > 1) {
+      hipLaunchKernelGGL(rows_reduce4_kernel,
+                         dim3((unsigned)std::min<int64_t>(((int64_t)rl->cap * C4 + 255) / 256, 8192)),
+                         dim3(256), 0, st, c);
+      D2MI_LAUNCH_CHECK();
+    }
+    return launch(p.tail, sp.tail);
+  }
   if (const int rc = launch(p.main, sp.main)) return rc;
   return launch(p.tail, sp.tail);
 }
@@ -1778,6 +1888,49 @@ extern "C" int d2mi_conv2d_nhwc_gated(const float* x, const float* w_packed, con
   D2MI_REQUIRE(gate != nullptr, "gated conv needs its gate");
   return conv_f32(x, w_packed, bias, nullptr, residual, gate, y, N, H, W, Cin, Cout, KH, KW,
                   stride, pad_beg, pad_end, flags, workspace, workspace_bytes, stream);
+}
+
+extern "C" int d2mi_conv2d_nhwc_rows(const float* x, const float* w_packed, const float* residual,
+                                     const float* gate, float* y, int N, int H, int W, int Cin,
+                                     int Cout, int KH, int KW, int stride, int pad_beg,
+                                     int pad_end, int flags, const void* census,
+                                     size_t census_bytes, int capacity, int dilate_k,
+                                     int dilate_pad, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  D2MI_REQUIRE((flags & ~(kSplit3 | kFlipTaps)) == 0,
+               "row-list conv flags: bit2 split-bf16 MFMA products, bit3 flipped weight taps");
+  if (conv_check_shape(N, H, W, Cin, Cout, KH, KW, stride)) return -1;
+  D2MI_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w_packed & 15) == 0,
+               "x and w must be 16-byte aligned");
+  D2MI_REQUIRE(capacity >= 0 && (long long)N * H * W < (1LL << 31), "bad row census shape");
+  // the census of x's N x H x W rows, as d2mi_row_census laid it out
+  const int cap = census_list_cap(N * H * W, capacity, dilate_k);
+  RowCensusSpace cs;
+  Workspace cw(const_cast<void*>(census), census_bytes);
+  cs.lay(cw, N * H * W, cap);
+  D2MI_REQUIRE(census != nullptr && cw.ok(), "row census workspace too small (%zu < %zu)",
+               census_bytes, cw.off);
+  ConvPlan p;
+  D2MI_REQUIRE(plan_conv({N, H, W, Cin, Cout, KH, KW, stride, pad_beg, pad_end}, flags,
+                         plan_operands(nullptr, residual, gate, y, nullptr, workspace),
+                         workspace_bytes, device_cus(), &p) == 0,
+               "conv output is empty");
+  // The list must have been dilated by this conv's own window, the conv map
+  // rows to rows (same size, stride 1), and the list be shorter than the main
+  // launch (whose slab then holds the compact partials); else the dense call.
+  const int cap_pad = (int)align_up((size_t)cap, 128);
+  const bool sparse = cap > 0 && dilate_k == KH && KH == KW && dilate_pad == pad_beg &&
+                      stride == 1 && p.OH == H && p.OW == W && conv_chunk(N, H, W, Cin) == N &&
+                      p.family != kConvStream1x1 && p.split3 && p.lds_epi && Cout % 4 == 0 &&
+                      p.main.tiles > 0 && p.main.m_base == 0 && cap_pad < p.main.m_end;
+  if (!sparse)
+    return conv_f32(x, w_packed, nullptr, nullptr, residual, gate, y, N, H, W, Cin, Cout, KH, KW,
+                    stride, pad_beg, pad_end, flags, workspace, workspace_bytes, stream);
+  const RowList rl = {cs.rows, cs.nrows, cap_pad};
+  const int rc = conv_core(x, w_packed, nullptr, nullptr, residual, gate, y, N, H, W, Cin, Cout,
+                           KH, KW, stride, pad_beg, pad_end, flags, workspace, workspace_bytes,
+                           stream, &rl);
+  return rc ? rc : 1;
 }
 
 extern "C" int d2mi_conv2d_nhwc(const float* x, const float* w_packed, const float* bias,

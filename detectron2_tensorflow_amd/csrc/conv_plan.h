@@ -342,6 +342,52 @@ struct WgradSpace {
   }
 };
 
+// The row census of a sparse gradient map of M pixel rows (conv_rows.hip):
+// one bit per 32-pixel chunk (kWgradKP) that holds a non-zero row, the
+// non-zero rows of each bitmap word, their total (read by
+// d2mi_conv2d_wgrad_rows, which lays out this head alone: list_cap 0); then,
+// with list_cap > 0, the sorted list of the output rows of a KxK stride-1
+// conv whose window holds a non-zero row (d2mi_conv2d_nhwc_rows) and the
+// flags and prefix sums it is compacted from.
+struct RowCensusSpace {
+  uint32_t* bitmap;    // [words]
+  int32_t* word_rows;  // [words]
+  int32_t* count;      // [1]
+  int words;
+  unsigned long long* rowbits;  // [16 * words] bit r % 64 of word r / 64: row r is non-zero
+  unsigned long long* dilbits;  // [16 * words] the same of the dilated (listed) rows
+  int32_t* dil_rows;            // [words] listed rows of each 1024-row block
+  int32_t* dil_prefix;          // [words] their exclusive prefix sum
+  int32_t* nrows;               // [1] listed rows (clamped to list_cap)
+  int32_t* rows;                // [list_cap] ascending
+  template <typename A>
+  void lay(A& a, int M, int list_cap) {
+    const int nchunks = (M + kWgradKP - 1) / kWgradKP;
+    words = (nchunks + 31) / 32;
+    bitmap = a.template take<uint32_t>(words);
+    word_rows = a.template take<int32_t>(words);
+    count = a.template take<int32_t>(1);
+    rowbits = dilbits = nullptr;
+    dil_rows = dil_prefix = nrows = rows = nullptr;
+    if (list_cap <= 0) return;
+    rowbits = a.template take<unsigned long long>((size_t)16 * words);
+    dilbits = a.template take<unsigned long long>((size_t)16 * words);
+    dil_rows = a.template take<int32_t>(words);
+    dil_prefix = a.template take<int32_t>(words);
+    nrows = a.template take<int32_t>(1);
+    rows = a.template take<int32_t>(list_cap);
+  }
+};
+// Capacity of the dilated row list: every one of `capacity` non-zero rows
+// lies in the windows of k * k output rows (0 = no list).
+inline int census_list_cap(int M, int capacity, int k) {
+  if (k <= 0) return 0;
+  return (int)std::max<long long>(1, std::min<long long>((long long)capacity * k * k, M));
+}
+// Most chunks of one pixel split that the bitmap weight gradient lists in LDS
+// (a split with more runs the dense kernel).
+constexpr int kWgradListCap = 2048;
+
 // flags: d2mi_conv2d_wgrad_ex's; operands: kOpAligned (dw), kOpWorkspace,
 // kOpWsAligned.  A missing or short workspace gives one split.
 inline int plan_wgrad(const ConvShape& s, int flags, int operands, size_t workspace_bytes,

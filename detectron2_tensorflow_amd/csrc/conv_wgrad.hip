@@ -54,6 +54,9 @@ struct WgradArgs {
   // re-reads meet in that XCD's L2 instead of eight.  Bit-identical (each
   // workgroup's (tile, split) work is unchanged, only its placement).
   int xcd;
+  // conv_wgrad_ws_kernel<.., LIST>: one bit per 32-pixel chunk, set where dy may
+  // hold a non-zero row (RowCensusSpace::bitmap; d2mi_conv2d_wgrad_rows)
+  const uint32_t* bitmap;
 };
 
 // (tile, split) of this workgroup: blockIdx as launched, or its XCD-contiguous
@@ -473,15 +476,29 @@ __global__ __launch_bounds__(256, OCC) void conv_wgrad_split_kernel(WgradArgs a,
 // its bias-gradient partial sums, reduced in the fixed order of the 128 x 128
 // kernel).  Same pixel order, product order and accumulation sequence as
 // conv_wgrad_split_kernel: bit-identical for equal pixel splits.
-template <int LD, bool INC = false>
+//
+// LIST (d2mi_conv2d_wgrad_rows): the workgroup first compacts the chunks of
+// its [c_begin, c_end) whose bit is set in a.bitmap into an ordered LDS list
+// (ballots and a fixed-order prefix over the waves: no atomics), and stagers
+// and compute waves walk that list instead of every chunk; the stagers seek
+// each listed chunk by division (no incremental cursor).  A chunk that is not
+// listed holds only zero dy rows: its products are +-0, added to accumulators
+// that start at +0 and can never become -0, so for finite x the sums (and the
+// bias sums) are bit-identical to the dense walk.  A split without a set
+// chunk still writes its zero slab.
+template <int LD, bool INC = false, bool LIST = false>
 __global__ __launch_bounds__(1024, 1) void conv_wgrad_ws_kernel(WgradArgs a, FastDiv fd_hw,
                                                                 FastDiv fd_w) {
+  static_assert(!(LIST && INC), "the listed chunks are not consecutive");
   constexpr int TM = 2, TN = 2, BM = 256, BN = 128, S = 2;
   constexpr int GA = BM / 4, GB = BN / 4;  // 4-channel groups
   constexpr int A_H = 3 * BM * LDW, B_H = 3 * BN * LDW;  // halfwords per stage
   constexpr int STAGE = A_H + B_H;                      // 36864 halfwords = 72 KiB
   __shared__ __attribute__((aligned(16))) uint16_t smem[S * STAGE];
   __shared__ float bred[8][BN];
+  // LIST: the set chunks of this split, as offsets from c_begin, ascending
+  __shared__ uint16_t clist[LIST ? kWgradListCap : 1];
+  __shared__ int wcnt[LIST ? 17 : 1];
 
   int tile, split;
   wgrad_tile_split(a, tile, split);
@@ -493,11 +510,36 @@ __global__ __launch_bounds__(1024, 1) void conv_wgrad_ws_kernel(WgradArgs a, Fas
   const int ci0 = cit * BM, co0 = cot * BN;
   const int c_begin = split * a.chunks_per_split;
   const int c_end = min(a.nchunks, c_begin + a.chunks_per_split);
-  const int nks = max(c_end - c_begin, 0);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int nks = max(c_end - c_begin, 0);
+  if constexpr (LIST) {
+    // ordered compaction, 1024 chunks per pass (host: nks <= kWgradListCap)
+    const int nall = nks;
+    int base = 0;
+    for (int i0 = 0; i0 < nall; i0 += 1024) {
+      const int i = i0 + tid;
+      bool set = false;
+      if (i < nall) {
+        const int ch = c_begin + i;
+        set = (a.bitmap[ch >> 5] >> (ch & 31)) & 1u;
+      }
+      const unsigned long long b = __ballot(set);
+      if (lane == 0) wcnt[wave] = __popcll(b);
+      __syncthreads();
+      int before = base;
+      for (int w = 0; w < 16; ++w) {
+        const int c = wcnt[w];
+        before += w < wave ? c : 0;
+        base += c;
+      }
+      if (set) clist[before + __popcll(b & ((1ull << lane) - 1ull))] = (uint16_t)i;
+      __syncthreads();
+    }
+    nks = __builtin_amdgcn_readfirstlane(base);
+  }
   const int wr = wave >> 1, wc = wave & 1;  // compute waves 0-7: 4 x 2
   const int li = lane & 31, lh = lane >> 5;
   const bool do_bias = a.dbias != nullptr && tap == 0 && cit == 0;
@@ -535,8 +577,12 @@ __global__ __launch_bounds__(1024, 1) void conv_wgrad_ws_kernel(WgradArgs a, Fas
     // addresses either way.
     const int clast = c_begin + max(nks, 1) - 1;
     int c_ch = c_begin;
-    int p0 = c_begin * KP + 4 * pga;   // first of this thread's 4 X pixels
-    int pb0 = c_begin * KP + 4 * pgb;  // (dY)
+    // LIST: position in the list of the chunk to load next (then the last again)
+    const int jlast = max(nks, 1) - 1;
+    int j_ld = 0;
+    const int c_first = (LIST && nks > 0) ? c_begin + clist[0] : c_begin;
+    int p0 = c_first * KP + 4 * pga;   // first of this thread's 4 X pixels
+    int pb0 = c_first * KP + 4 * pgb;  // (dY)
     int oy0 = 0, ox0 = 0;
     if (INC) {
       const int r2 = p0 - (int)fdiv((uint32_t)p0, fd_hw) * (a.OH * a.OW);
@@ -575,7 +621,15 @@ __global__ __launch_bounds__(1024, 1) void conv_wgrad_ws_kernel(WgradArgs a, Fas
         const uint32_t offb = (co_ok & (pb0 + q < a.P)) ? boff + (uint32_t)(q * a.Cout * 4) : kOOB;
         lb[q] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(yr, offb, 0, 0));
       }
-      if (c_ch < clast) {  // advance to the next chunk (uniform condition)
+      if constexpr (LIST) {
+        if (j_ld < jlast) {  // seek the next listed chunk (uniform condition)
+          ++j_ld;
+          const int ch = c_begin + clist[j_ld];
+          p0 = ch * KP + 4 * pga;
+          pb0 = ch * KP + 4 * pgb;
+          boff = (uint32_t)(pb0 * a.Cout + co) * 4u;
+        }
+      } else if (c_ch < clast) {  // advance to the next chunk (uniform condition)
         ++c_ch;
         p0 += KP;
         pb0 += KP;
@@ -798,10 +852,14 @@ extern "C" int d2mi_conv2d_wgrad_plan(int N, int H, int W, int Cin, int Cout, in
   return emit_plan(v, (int)(sizeof(v) / sizeof(v[0])), out, out_len);
 }
 
-extern "C" int d2mi_conv2d_wgrad_ex(const float* x, const float* dy, float* dw_hwio,
-                                    float* dbias, int N, int H, int W, int Cin, int Cout, int KH,
-                                    int KW, int stride, int pad_beg, int pad_end, int flags,
-                                    void* workspace, size_t workspace_bytes, void* stream) {
+// d2mi_conv2d_wgrad_ex, and with a chunk bitmap d2mi_conv2d_wgrad_rows: the
+// same plan either way.  Returns 1 when the bitmap kernel ran, 0 after the
+// dense launch (kernels other than the warp-specialised one ignore the
+// bitmap, and so does a split of more than kWgradListCap chunks).
+static int wgrad_launch(const float* x, const float* dy, float* dw_hwio, float* dbias, int N,
+                        int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_beg,
+                        int pad_end, int flags, const uint32_t* bitmap, void* workspace,
+                        size_t workspace_bytes, void* stream) {
   auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
   WgradPlan p;
   if (wgrad_plan_checked(N, H, W, Cin, Cout, KH, KW, stride, pad_beg, pad_end, flags,
@@ -851,7 +909,12 @@ extern "C" int d2mi_conv2d_wgrad_ex(const float* x, const float* dy, float* dw_h
   }
   const FastDiv fhw = make_fastdiv((uint32_t)(a.OH * a.OW)), fw = make_fastdiv((uint32_t)a.OW);
   const int tm = p.TM, tn = p.TN;
-  if (p.kernel == kWgradWS2)
+  const bool listed = bitmap != nullptr && p.chunks_per_split <= kWgradListCap &&
+                      (p.kernel == kWgradWS2 || p.kernel == kWgradWSInc || p.kernel == kWgradWS);
+  a.bitmap = listed ? bitmap : nullptr;
+  if (listed)
+    hipLaunchKernelGGL((conv_wgrad_ws_kernel<1, false, true>), grid, dim3(1024), 0, st, a, fhw, fw);
+  else if (p.kernel == kWgradWS2)
     hipLaunchKernelGGL((conv_wgrad_ws_kernel<2>), grid, dim3(1024), 0, st, a, fhw, fw);
   else if (p.kernel == kWgradWSInc)
     hipLaunchKernelGGL((conv_wgrad_ws_kernel<1, true>), grid, dim3(1024), 0, st, a, fhw, fw);
@@ -876,7 +939,7 @@ extern "C" int d2mi_conv2d_wgrad_ex(const float* x, const float* dy, float* dw_h
   else
     hipLaunchKernelGGL((conv_wgrad_kernel<1, 1>), grid, dim3(256), 0, st, a);
   D2MI_LAUNCH_CHECK();
-  if (p.reduce == kReduceNone) return 0;
+  if (p.reduce == kReduceNone) return listed ? 1 : 0;
   const size_t total = (size_t)KH * KW * Cin * Cout;
   const int accum = (flags & kPlanAccum) != 0;
   if (p.reduce == kReduceFloat4)
@@ -887,7 +950,36 @@ extern "C" int d2mi_conv2d_wgrad_ex(const float* x, const float* dy, float* dw_h
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(p.reduce_grid), dim3(256), 0, st, a.partial,
                        a.splits, total, dw_hwio, a.pbias, Cout, dbias, accum);
   D2MI_LAUNCH_CHECK();
-  return 0;
+  return listed ? 1 : 0;
+}
+
+extern "C" int d2mi_conv2d_wgrad_ex(const float* x, const float* dy, float* dw_hwio,
+                                    float* dbias, int N, int H, int W, int Cin, int Cout, int KH,
+                                    int KW, int stride, int pad_beg, int pad_end, int flags,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+  return wgrad_launch(x, dy, dw_hwio, dbias, N, H, W, Cin, Cout, KH, KW, stride, pad_beg, pad_end,
+                      flags, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int d2mi_conv2d_wgrad_rows(const float* x, const float* dy, float* dw_hwio,
+                                      float* dbias, int N, int H, int W, int Cin, int Cout, int KH,
+                                      int KW, int stride, int pad_beg, int pad_end, int flags,
+                                      const void* census, size_t census_bytes, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  int OH, OW;
+  D2MI_REQUIRE(N > 0 && H > 0 && W > 0 && KH > 0 && KW > 0 && stride > 0 &&
+                   conv_dims(H, W, KH, KW, stride, pad_beg, pad_end, OH, OW) == 0 &&
+                   (long long)N * OH * OW < (1LL << 31),
+               "bad conv shape");
+  // the census of dy's N x OH x OW pixel rows, as d2mi_row_census laid it out
+  RowCensusSpace cs;
+  Workspace carve(const_cast<void*>(census), census_bytes);
+  cs.lay(carve, N * OH * OW, 0);  // (the head of the layout: no list needed here)
+  D2MI_REQUIRE(census != nullptr && carve.ok(), "row census workspace too small (%zu < %zu)",
+               census_bytes, carve.off);
+  D2MI_REQUIRE(((uintptr_t)census & 3) == 0, "the row census must be 4-byte aligned");
+  return wgrad_launch(x, dy, dw_hwio, dbias, N, H, W, Cin, Cout, KH, KW, stride, pad_beg, pad_end,
+                      flags, cs.bitmap, workspace, workspace_bytes, stream);
 }
 
 

@@ -45,8 +45,10 @@ def same_pads(kernel_size, rate=1):
     return pb, pad_total - pb
 
 
-def _dgrad(gy, w, x_shape, stride, pb, pe, relu_gate=None, add=None, add2=None):
-    """Input gradient (+ add, then the relu_gate mask, when given).  Stride 1:
+def _dgrad(gy, w, x_shape, stride, pb, pe, relu_gate=None, add=None, add2=None, census=None):
+    """Input gradient (+ add, then the relu_gate mask, when given).  census: an
+    ops.RowCensus of gy (a declared handoff.RowBound) for the stride-1 MFMA
+    path, which then computes only the rows near a non-zero gy row.  Stride 1:
     a forward conv of gy with the spatially flipped kernel — whose HWIO layout IS the packed [KH, KW, out', in'] layout
     of the transposed conv, flipped by the kernel's tap indexing (kFlipTaps) —
     on the MFMA kernel, padded (KH-1-pb, KH-1-pe).
@@ -66,7 +68,7 @@ def _dgrad(gy, w, x_shape, stride, pb, pe, relu_gate=None, add=None, add2=None):
             # the flip is an index flip inside the kernel (no flipped copy)
             return ops.conv2d_nhwc(gy, w.detach().contiguous(), None, 1,
                                    (KH - 1 - pb, KH - 1 - pe), flip_taps=KH > 1,
-                                   residual=add, relu_gate=relu_gate)
+                                   residual=add, relu_gate=relu_gate, census=census)
         if KH == 1 and pb == 0 and pe == 0:
             g = ops.conv2d_nhwc(gy, w.detach().contiguous(), None, 1, (0, 0))
             if Cin % 4 == 0:  # zero holes + scatter (+ add) (+ gate) in one pass
@@ -87,8 +89,12 @@ def _dgrad(gy, w, x_shape, stride, pb, pe, relu_gate=None, add=None, add2=None):
 _WGRAD_1X1_MIN_P = int(os.environ.get("D2MI_WGRAD_1X1_MIN_P", "8192"))
 
 
-def _wgrad(x, gy, w_shape, stride, pb, pe, want_bias=False, accumulate_into=None):
+def _wgrad(x, gy, w_shape, stride, pb, pe, want_bias=False, accumulate_into=None, census=None):
     """(weight gradient HWIO, bias gradient or None).
+
+    census: an ops.RowCensus of gy's pixel rows (a declared handoff.RowBound),
+    or None: the MFMA wgrad of a KxK conv then walks only the 32-pixel chunks
+    that hold a non-zero row (bit-identical); every other path ignores it.
 
     accumulate_into: (gw, gb) of earlier calls of the same shared weight
     (gb None without a bias): this call's gradient is added into them --
@@ -110,8 +116,9 @@ def _wgrad(x, gy, w_shape, stride, pb, pe, want_bias=False, accumulate_into=None
     def mfma(k, pads):
         if want_bias and (acc_w is None or acc_b is not None):
             acc = (acc_w, acc_b) if acc_w is not None else None
-            return ops.conv2d_wgrad(x, gy, k, stride, pads, with_bias=True, accumulate_into=acc)
-        return ops.conv2d_wgrad(x, gy, k, stride, pads, accumulate_into=acc_w), None
+            return ops.conv2d_wgrad(x, gy, k, stride, pads, with_bias=True, accumulate_into=acc,
+                                    census=census)
+        return ops.conv2d_wgrad(x, gy, k, stride, pads, accumulate_into=acc_w, census=census), None
 
     def added(gw):  # a path without the fused accumulate
         return (gw if acc_w is None else acc_w.add_(gw)), None
@@ -133,14 +140,15 @@ def _wgrad(x, gy, w_shape, stride, pb, pe, want_bias=False, accumulate_into=None
     return added(gw.permute(2, 3, 1, 0))
 
 
-def _wgrad_shared(acc, x, gy, w_shape, stride, pb, pe, want_bias):
+def _wgrad_shared(acc, x, gy, w_shape, stride, pb, pe, want_bias, census=None):
     """One call's share of a weight used by several calls of one forward
     (``wacc``, a handoff.LevelAccumulator: the RPN head's 3x3 over the FPN
     levels): its (gw, gb) go into the accumulator (the reduce pass adds them:
     old + new, autograd's order for the summed gradients); every call but the
     last returns (None, None), the last the sums."""
     def step(buf):
-        gw, gb = _wgrad(x, gy, w_shape, stride, pb, pe, want_bias, accumulate_into=buf)
+        gw, gb = _wgrad(x, gy, w_shape, stride, pb, pe, want_bias, accumulate_into=buf,
+                        census=census)
         if want_bias and gb is None:
             cs = ops.column_sum(gy)
             gb = cs if buf is None or buf[1] is None else buf[1].add_(cs)
@@ -158,15 +166,15 @@ def _wgrad_shared(acc, x, gy, w_shape, stride, pb, pe, want_bias):
 WGRAD_STREAM = {}
 
 
-def _wgrad_of(ctx, x, gy, w, stride, pb, pe, want_b):
+def _wgrad_of(ctx, x, gy, w, stride, pb, pe, want_b, census=None):
     """(weight, bias) gradient of _ConvMFMAFn's backward, None where not needed."""
     gw = gb = None
     wacc = ctx.links.wacc if ctx.links is not None else None
     if ctx.needs_input_grad[1] and wacc is not None:
-        gw, gb = _wgrad_shared(wacc, x, gy, w.shape, stride, pb, pe, want_b)
+        gw, gb = _wgrad_shared(wacc, x, gy, w.shape, stride, pb, pe, want_b, census)
     else:
         if ctx.needs_input_grad[1]:
-            gw, gb = _wgrad(x, gy, w.shape, stride, pb, pe, want_b)
+            gw, gb = _wgrad(x, gy, w.shape, stride, pb, pe, want_b, census=census)
         if want_b and gb is None:
             gb = ops.column_sum(gy)
     return gw, gb
@@ -231,6 +239,11 @@ class _ConvMFMAFn(torch.autograd.Function):
             gres = None
         gx = gw = gb = None
         want_b = has_bias and ctx.needs_input_grad[2]
+        # the row census of gy, where this call's output gradient has a
+        # declared row bound (handoff.RowBound: None = dense)
+        census = None
+        if links is not None and links.rows is not None:
+            census = links.rows[0].take(links.rows[1])
         side = WGRAD_STREAM.get("stream")
         main = None
         if side is not None and ctx.needs_input_grad[1] and gy.is_cuda:
@@ -239,22 +252,24 @@ class _ConvMFMAFn(torch.autograd.Function):
             # graph has both branches); joined at the end of this backward
             main = torch.cuda.current_stream(gy.device)
             side.wait_stream(main)
+            if census is not None:  # (made on this stream, read on the side one)
+                census.ws.record_stream(side)
             with torch.cuda.stream(side):
-                gw, gb = _wgrad_of(ctx, x, gy, w, stride, pb, pe, want_b)
+                gw, gb = _wgrad_of(ctx, x, gy, w, stride, pb, pe, want_b, census)
         if ctx.needs_input_grad[0] and links is None:
             gx = _dgrad(gy, w, x.shape, stride, pb, pe)
         elif ctx.needs_input_grad[0]:
             plan = links.plan(_gate_eligible(w.shape, stride, pb, pe))
             gx = plan.finish(_dgrad(gy, w, x.shape, stride, pb, pe,
                                     relu_gate=x if plan.gate else None,
-                                    add=plan.add, add2=plan.add2))
+                                    add=plan.add, add2=plan.add2, census=census))
         if main is not None:
             main.wait_stream(side)
             for t in (gw, gb):  # (made on the side stream, used on this one)
                 if t is not None:
                     t.record_stream(main)
         else:
-            gw, gb = _wgrad_of(ctx, x, gy, w, stride, pb, pe, want_b)
+            gw, gb = _wgrad_of(ctx, x, gy, w, stride, pb, pe, want_b, census)
         return gx, gw, gb, None, None, None, None, gtd, gres, None, None
 
 
@@ -525,14 +540,15 @@ class Conv2D(Layer):
 
     def call(self, inputs, topdown=None, residual=None, relu_after_add=False, final_relu=False,
              relu_input_sole_consumer=False, res_grad_to=None, grad_from=None, pair_grad=None,
-             raw=False, join=None, wacc=None):
+             raw=False, join=None, wacc=None, rows=None):
         """topdown: fused + up2(topdown) (FPN merge); residual: fused + residual;
         relu_after_add: the layer's ReLU runs after those adds; final_relu: an
         extra ReLU after the adds for a layer without activation (the
         bottleneck's relu(conv3(x) + shortcut), blocks.py:143-186).
         relu_input_sole_consumer, res_grad_to / grad_from (a handoff.Slot),
-        pair_grad / join (a handoff.Pair), wacc (a handoff.LevelAccumulator):
-        the gradient hand-offs of layers/handoff.py."""
+        pair_grad / join (a handoff.Pair), wacc (a handoff.LevelAccumulator),
+        rows ((handoff.RowBound, level) of the output's gradient): the gradient
+        hand-offs of layers/handoff.py."""
         impl = self.impl
         if impl == "auto":
             impl = "mfma" if self._mfma_eligible(inputs) else "torch"
@@ -565,7 +581,7 @@ class Conv2D(Layer):
             if packed is None:
                 packed = self.packed_weights(w)
             links = handoff.Links(bool(relu_input_sole_consumer), res_grad_to, grad_from,
-                                  pair_grad, join, wacc)
+                                  pair_grad, join, wacc, rows)
             ret = _ConvMFMAFn.apply(inputs, w, b, packed, self.stride, pads,
                                     fuse_relu, topdown, residual, relu_after_add, links)
             if raw:  # the conv (+ bias) alone: the caller applies the normalizer / activation

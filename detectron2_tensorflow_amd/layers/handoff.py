@@ -64,6 +64,14 @@ order for the summed gradients) or defers its (input, gradient) pair; every
 arrival but the n-th gets nothing, the n-th the result, and the accumulator
 starts over (a second backward of the same graph).
 
+``RowBound`` -- a bound on the non-zero rows of a gradient that only its
+producer can know (the RPN loss: the sampled anchors), declared by that
+producer and handed down to the backwards that can skip the zero rows (the
+RPN head's shared 3x3: a row census per level, made where the gradient is
+still 16 wide, then a weight gradient over the non-zero 32-pixel chunks and a
+data gradient over the rows whose 3x3 window holds a non-zero row).
+Undeclared means dense everywhere.
+
 ``PoolerShare`` -- the box and mask poolers of a training step, which pool the
 SAME maps.  Merged backward: the first arrival leaves its (boxes, box_ind,
 grad_out, params) as set 0 and the second runs one backward over both sets.
@@ -129,6 +137,7 @@ RELU = "_d2mi_relu_info"         # a fused-ReLU conv output -> its ReluTag
 STAGE_PAIR = "_d2mi_pair"        # a bottleneck input -> its conv1 / shortcut Pair
 TD_PAIR = "_d2mi_td_pair"        # an FPN merged map -> its output conv's Pair
 LEVEL_PAIR = "_d2mi_grad_pair"   # an FPN level -> its RPN conv / ROI pooler Pair
+ROW_BOUND = "_d2mi_row_bound"    # the RPN head's concatenated logits -> its RowBound
 
 
 def tag(t, name, value):
@@ -277,13 +286,14 @@ class Plan:
 class Links:
     """One conv call's ends of the hand-offs (all optional)."""
     __slots__ = ("sole_consumer", "res_grad_to", "grad_from", "pair", "join", "wacc", "in_tag",
-                 "producer_tag", "td_pair")
+                 "producer_tag", "td_pair", "rows")
 
     def __init__(self, sole_consumer=False, res_grad_to=None, grad_from=None, pair=None,
-                 join=None, wacc=None):
+                 join=None, wacc=None, rows=None):
         self.sole_consumer = sole_consumer
         self.res_grad_to, self.grad_from = res_grad_to, grad_from
         self.pair, self.join, self.wacc = pair, join, wacc
+        self.rows = rows  # (RowBound, level) of the output gradient, or None
         self.in_tag = self.producer_tag = self.td_pair = None
 
     def bind(self, x, topdown, has_residual):
@@ -403,6 +413,84 @@ class LevelAccumulator:
         out = self.deferred
         self.clear()
         return out
+
+
+class RowBound:
+    """A declared bound on the non-zero pixel rows of a gradient, per image,
+    carried from the loss that knows it to the backwards that can use it (the
+    RPN head: the loss has a gradient on the sampled anchors only, the head's
+    fused 1x1 maps a zero row to a zero row, and it is the sole consumer of
+    the shared 3x3's output).  One object per head forward, ``n`` levels.
+
+    Undeclared (``declare`` never called): every level is dense, as without
+    the object.  Declared: the 1x1's backward at level l runs a row census
+    where ``wants_census`` and ``publish``es it (None = dense) for level l;
+    the 3x3's backward ``take``s it, once, after it was published, and hands
+    it to its weight and data gradients.  ``dilate``: (k, leading pad) of that
+    data gradient's window, by which the census dilates its row list.  Nothing is
+    ever inferred from the gradient's values: a false declaration sets the
+    device error word (the census counts against ``capacity``).
+
+    ``sparse_launches`` counts the launches that used a census (tests)."""
+    __slots__ = ("n", "dilate", "rows_per_image", "_published", "sparse_launches")
+
+    _EMPTY = object()
+
+    def __init__(self, n, dilate=None):
+        self.n = n
+        # (k, leading pad) of the stride-1 conv window the census row lists are
+        # dilated by: the consumer's data gradient (None: no lists)
+        self.dilate = dilate
+        self.rows_per_image = None
+        self._published = [RowBound._EMPTY] * n
+        self.sparse_launches = 0
+
+    @property
+    def declared(self):
+        return self.rows_per_image is not None
+
+    def declare(self, rows_per_image):
+        rows_per_image = int(rows_per_image)
+        if rows_per_image <= 0:
+            raise ValueError("RowBound: rows_per_image must be positive")
+        self.rows_per_image = rows_per_image
+
+    def capacity(self, N):
+        """Most non-zero rows of a level's gradient over N images."""
+        return N * self.rows_per_image if self.declared else None
+
+    def list_capacity(self, N):
+        """Most rows of a level's dilated list: k * k per non-zero row."""
+        k = self.dilate[0] if self.dilate else 0
+        return k * k * self.capacity(N) if self.declared else None
+
+    def wants_census(self, N, M):
+        """A level of M pixel rows over N images is worth a census: even with
+        every non-zero row's 3x3 neighbourhood counted, most rows are zero."""
+        return self.declared and 9 * N * self.rows_per_image < M
+
+    # wants_list: the list's capacity (k * k rows per non-zero row) against the
+    # level's rows.  Measured on the MI355X (DESIGN.md, "Sparse RPN-head
+    # backward"): the row-list data gradient wins clearly at 1/29 of the rows
+    # (p2), about breaks even at 1/7 (p3) and loses at 1/2 (p4), where the fill,
+    # the list's two extra census launches and the under-filled grid cost more
+    # than the dense launch.
+    LIST_MAX_FRACTION = 1.0 / 16
+
+    def wants_list(self, N, M):
+        """The census of a level of M rows should carry the dilated row list."""
+        return (self.dilate is not None and self.wants_census(N, M)
+                and self.list_capacity(N) <= M * type(self).LIST_MAX_FRACTION)
+
+    def publish(self, level, census):
+        self._published[level] = census
+
+    def take(self, level):
+        census = self._published[level]
+        if census is RowBound._EMPTY:
+            raise HandoffError(f"row bound: level {level} was not published (or taken twice)")
+        self._published[level] = RowBound._EMPTY
+        return census
 
 
 class PoolerShare:

@@ -683,8 +683,13 @@ _NARROW_SPLIT = os.environ.get("D2MI_NARROW_SPLIT", "1") != "0"
 
 def conv2d_nhwc(x, w_packed, bias=None, stride=1, pad=(0, 0), relu=False, topdown=None,
                 residual=None, relu_after_add=False, math_mode=None, flip_taps=False,
-                relu_gate=None, out=None):
+                relu_gate=None, out=None, census=None):
     """MFMA implicit-GEMM conv: x [N,H,W,Cin], w_packed [KH,KW,Cout,Cin].
+    census: a RowCensus of x's pixel rows whose list was dilated by this
+    conv's window (a stride-1 same-size dgrad of a sparse gradient, no bias /
+    relu / top-down): d2mi_conv2d_nhwc_rows computes the listed output rows
+    only and fills the rest with the epilogue of zero -- bit-identical; timed
+    as "conv2d_rows" when the row-list launch ran.
     relu_after_add: relu(conv + bias + residual/topdown) instead of
     relu(conv + bias) + residual/topdown.  math_mode: "f32" | "split" (None:
     CONV_MATH).  flip_taps: use the spatially flipped kernel (w_packed[KH-1-i, KW-1-j]).
@@ -738,7 +743,22 @@ def conv2d_nhwc(x, w_packed, bias=None, stride=1, pad=(0, 0), relu=False, topdow
                                                               int(stride), int(pb), int(pe))
     ws = _C.scratch(wsb, x.device) if wsb else None
     st = _C.stream_of(x.device)
-    if relu_gate is not None:
+    if (census is not None and census.dilate is not None and bias is None and topdown is None
+            and not relu and math_mode == "split" and census.shape == (N, H, W)):
+        ev = KernelTimer.start()
+        rc = lib.d2mi_conv2d_nhwc_rows(_C.ptr(x), _C.ptr(w_packed), _C.ptr(residual),
+                                       _C.ptr(relu_gate), _C.ptr(y), N, H, W, Cin, Cout, KH, KW,
+                                       int(stride), int(pb), int(pe), flags, _C.ptr(census.ws),
+                                       census.ws.numel(), census.capacity, census.dilate[0],
+                                       census.dilate[1], _C.ptr(ws), wsb, st)
+        if rc == 1:  # the row-list launch ran: not a dense launch (its own timing name)
+            KernelTimer.stop(ev, "conv2d_rows", 0.0)
+            if KernelTimer.detail and ev is not None:
+                KernelTimer.stop(ev, f"conv_rows {N}x{H}x{W}x{Cin}->{Cout} k{KH} s{stride}", 0.0)
+            census.used()
+            return y
+        rc = min(rc, 0)
+    elif relu_gate is not None:
         ev = KernelTimer.start()
         rc = lib.d2mi_conv2d_nhwc_gated(_C.ptr(x), _C.ptr(w_packed), _C.ptr(bias),
                                         _C.ptr(residual), _C.ptr(relu_gate), _C.ptr(y), N,
@@ -834,14 +854,104 @@ def conv2d_nhwc_levels(xs, w_packed, bias=None, stride=1, pad=(0, 0), relu=False
     return ys
 
 
+class RowCensus:
+    """The row census of a sparse gradient map [N, H, W, C] (d2mi_row_census):
+    its device workspace ``ws`` and, for tests and tools, views of its parts.
+    ``dilate``: (k, pad) of the stride-1 conv window its row list was dilated
+    by, or None (no list).  ``owner``: an object whose ``sparse_launches``
+    counts the launches that used this census (a handoff.RowBound), or None."""
+    __slots__ = ("ws", "shape", "capacity", "dilate", "owner", "_layout")
+
+    def __init__(self, ws, shape, capacity, dilate=None, owner=None):
+        self.ws, self.shape, self.capacity = ws, tuple(shape), int(capacity)
+        self.dilate, self.owner = dilate, owner
+        self._layout = None
+
+    def _parts(self):
+        if self._layout is None:
+            out = (_C.ctypes.c_int64 * 7)()
+            k = self.dilate[0] if self.dilate else 0
+            _C.check(_C.lib().d2mi_row_census_layout(*self.shape, self.capacity, k, out, 7),
+                     "d2mi_row_census_layout")
+            self._layout = tuple(out)
+        return self._layout
+
+    def _i32(self, off, n):
+        return self.ws[off:off + 4 * n].view(torch.int32)
+
+    @property
+    def bitmap(self):
+        """int32 [words]: bit c % 32 of word c // 32 = chunk c holds a non-zero row."""
+        return self._i32(self._parts()[0], self._parts()[1])
+
+    @property
+    def count(self):
+        """int32 [1]: the number of non-zero rows."""
+        return self._i32(self._parts()[3], 1)
+
+    @property
+    def list_capacity(self):
+        return self._parts()[6]
+
+    @property
+    def nrows(self):
+        """int32 [1]: the number of listed (dilated) rows, clamped to list_capacity."""
+        return self._i32(self._parts()[4], 1)
+
+    @property
+    def rows(self):
+        """int32 [list_capacity]: the listed rows, ascending (the first nrows are valid)."""
+        return self._i32(self._parts()[5], self._parts()[6])
+
+    def used(self):
+        if self.owner is not None:
+            self.owner.sparse_launches += 1
+
+
+_CENSUS_WS = {}
+
+
+def row_census_workspace_size(N, H, W, capacity=0, dilate_k=0):
+    key = (int(N), int(H), int(W), int(capacity), int(dilate_k))
+    n = _CENSUS_WS.get(key)
+    if n is None:
+        n = _CENSUS_WS[key] = _C.lib().d2mi_row_census_workspace_size(*key)
+    return n
+
+
+def row_census(g, capacity, dilate=None, owner=None):
+    """RowCensus of g [N, H, W, C] (C % 4 == 0): which 32-pixel chunks hold a
+    non-zero row, how many rows are non-zero (more than ``capacity`` sets the
+    device error word: a declared bound was false) and, with dilate = (k, pad),
+    the sorted list of the output rows of a k x k stride-1 conv over g (pad
+    leading zeros) whose window holds a non-zero row.  The census owns its
+    workspace: it lives until its last reader has run."""
+    g = _f32c(g)
+    _C.require_device(g)
+    N, H, W, C = g.shape
+    k, pad = (int(dilate[0]), int(dilate[1])) if dilate else (0, 0)
+    nbytes = row_census_workspace_size(N, H, W, capacity, k)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
+    ev = KernelTimer.start()
+    rc = _C.lib().d2mi_row_census(_C.ptr(g), N, H, W, C, int(capacity), k, pad, _C.ptr(ws), nbytes,
+                                  _C.stream_of(g.device))
+    KernelTimer.stop(ev, "row_census", 4.0 * g.numel())
+    _C.check(rc, "d2mi_row_census")
+    return RowCensus(ws, (N, H, W), capacity, (k, pad) if k else None, owner)
+
+
 def conv2d_wgrad(x, dy, kernel_size, stride=1, pad=(0, 0), with_bias=False, math_mode=None,
-                 accumulate_into=None):
+                 accumulate_into=None, census=None):
     """HWIO weight gradient of conv2d_nhwc on the MFMA wgrad kernel; with_bias
     also returns the bias gradient (dy summed over pixels) from the same pass.
     math_mode: "f32" | "split" (None: CONV_MATH), as conv2d_nhwc.
     accumulate_into: the (dw, db) -- or dw -- of an earlier call to add this
     one's gradient into (d2mi_conv2d_wgrad_ex bit 3: old + new in the reduce
-    pass, autograd's order for a weight shared by several calls)."""
+    pass, autograd's order for a weight shared by several calls).
+    census: a RowCensus of dy's pixel rows (or of a superset of its non-zero
+    rows): d2mi_conv2d_wgrad_rows walks only the set chunks -- the same plan,
+    bit-identical for finite x; timed as "conv2d_wgrad_rows" when the bitmap
+    kernel ran (the plan's other kernels run dense and are timed as such)."""
     math_mode = math_mode or CONV_MATH
     if math_mode not in ("f32", "split"):
         raise ValueError(f"conv math must be 'f32' or 'split', got {math_mode!r}")
@@ -849,6 +959,8 @@ def conv2d_wgrad(x, dy, kernel_size, stride=1, pad=(0, 0), with_bias=False, math
     _C.require_device(x, dy)
     N, H, W, Cin = x.shape
     Cout = dy.shape[-1]
+    if census is not None and census.shape != tuple(dy.shape[:3]):
+        raise ValueError(f"row census of {census.shape} pixels for a gradient of {tuple(dy.shape[:3])}")
     KH = KW = int(kernel_size)
     pb, pe = pad
     if accumulate_into is not None:
@@ -868,8 +980,20 @@ def conv2d_wgrad(x, dy, kernel_size, stride=1, pad=(0, 0), with_bias=False, math
     ws = _C.scratch(wsb, x.device) if wsb else None
     ev = KernelTimer.start()
     flags = (4 if math_mode == "split" else 0) | (8 if accumulate_into is not None else 0)
-    rc = _C.lib().d2mi_conv2d_wgrad_ex(_C.ptr(x), _C.ptr(dy), _C.ptr(dw), _C.ptr(db), *args,
-                                       flags, _C.ptr(ws), wsb, _C.stream_of(x.device))
+    if census is not None:
+        rc = _C.lib().d2mi_conv2d_wgrad_rows(_C.ptr(x), _C.ptr(dy), _C.ptr(dw), _C.ptr(db), *args,
+                                             flags, _C.ptr(census.ws), census.ws.numel(),
+                                             _C.ptr(ws), wsb, _C.stream_of(x.device))
+        if rc == 1:  # the bitmap kernel ran: not a dense launch (its own timing name)
+            KernelTimer.stop(ev, "conv2d_wgrad_rows", 0.0)
+            if KernelTimer.detail and ev is not None:
+                KernelTimer.stop(ev, f"wgrad_rows {N}x{H}x{W}x{Cin}->{Cout} k{KH} s{stride}", 0.0)
+            census.used()
+            return (dw, db) if with_bias else dw
+        rc = min(rc, 0)
+    else:
+        rc = _C.lib().d2mi_conv2d_wgrad_ex(_C.ptr(x), _C.ptr(dy), _C.ptr(dw), _C.ptr(db), *args,
+                                           flags, _C.ptr(ws), wsb, _C.stream_of(x.device))
     fl = 2.0 * dy.numel() * KH * KW * Cin
     group = "conv2d_wgrad_split" if flags & 4 else "conv2d_wgrad_mfma"
     KernelTimer.stop(ev, group, fl)

@@ -9,6 +9,7 @@ level NMS, per-image top-k(post) and padding — in one fixed launch sequence.
 import torch
 
 from ...layers import Conv2D, Layer
+from ...layers.convolutional import same_pads
 from ...layers import initializers as init
 from ...layers import handoff, ops
 from ...layers.loss import smooth_l1_loss
@@ -36,6 +37,14 @@ class StandardRPNHead(Layer):
     # levels in one buffer (the MFMA wgrad's reduce adds each level into it;
     # layers/convolutional.py:_wgrad_shared) -- autograd's per-level adds go
     ACC_CONV_LEVELS = True
+    # True: the head hands a handoff.RowBound from the loss to its backwards.
+    # When RPN.losses declares the sampled anchors per image on it, the levels
+    # where that leaves most pixel rows without a gradient run a row census
+    # of the 16-wide gradient; the shared 3x3's weight gradient then walks only
+    # the non-zero 32-pixel chunks and its data gradient computes only the rows
+    # whose window holds a non-zero row (both bit-identical to the dense
+    # launches).  False: dense (A/B, tests)
+    SPARSE_ROWS = True
 
     def __init__(self, cfg, input_shape, **kwargs):
         super().__init__(**kwargs)
@@ -96,12 +105,17 @@ class StandardRPNHead(Layer):
                 if fuse and torch.is_grad_enabled() and _RPNHead1x1Fn.ACC_LEVELS else None)
         cacc = (handoff.LevelAccumulator(len(features), "shared conv weight-gradient calls")
                 if fuse and torch.is_grad_enabled() and StandardRPNHead.ACC_CONV_LEVELS else None)
+        # (the 3x3's dgrad window: its row list is dilated by it)
+        k = self.conv.kernel_size
+        rows = (handoff.RowBound(len(features), dilate=(k, k - 1 - same_pads(k)[0]))
+                if fuse and torch.is_grad_enabled() and StandardRPNHead.SPARSE_ROWS else None)
         ys = []
         pairs = [handoff.tagged(x, handoff.LEVEL_PAIR) for x in features]
         for li, x in enumerate(features):
             # a level the ROI poolers also read hands its input gradient over
             # (GeneralizedRCNN tags them with a handoff.Pair)
-            share = self.conv(x, pair_grad=pairs[li], wacc=cacc)
+            share = self.conv(x, pair_grad=pairs[li], wacc=cacc,
+                              rows=(rows, li) if rows is not None else None)
             if fuse:
                 # the fused 1x1 is the declared SOLE consumer of the 3x3's ReLU
                 # output (its dgrad applies the ReLU mask, _RPNHead1x1Fn): the
@@ -115,7 +129,8 @@ class StandardRPNHead(Layer):
                 ys.append(_RPNHead1x1Fn.apply(share, self.objectness_logits.weights,
                                               self.objectness_logits.bias,
                                               self.anchor_deltas.weights, self.anchor_deltas.bias,
-                                              w16, wp, b16, wacc))
+                                              w16, wp, b16, wacc,
+                                              (rows, li) if rows is not None else None))
             else:
                 logits.append(self.objectness_logits(share))
                 deltas.append(self.anchor_deltas(share))
@@ -137,6 +152,8 @@ class StandardRPNHead(Layer):
                 deltas.append(pd[:, off * A:(off + H * W) * A].view(N, H, W, 4 * A))
                 off += H * W
             logits.concat = deltas.concat = (pl, pd)
+            if rows is not None:  # for the loss to declare its bound on (RPN.losses)
+                handoff.tag(pl, handoff.ROW_BOUND, rows)
         return rpn_features, logits, deltas
 
 
@@ -187,7 +204,7 @@ class _RPNHead1x1Fn(torch.autograd.Function):
     LEVELS_ONE_LAUNCH = True
 
     @staticmethod
-    def forward(ctx, share, wo, bo, wd, bd, w16, wp, b16, wacc=None):
+    def forward(ctx, share, wo, bo, wd, bd, w16, wp, b16, wacc=None, rows=None):
         y = ops.conv2d_nhwc(share, wp, b16)
         A, D = wo.shape[3], wd.shape[3]
         ctx.save_for_backward(share, w16)
@@ -195,6 +212,7 @@ class _RPNHead1x1Fn(torch.autograd.Function):
         ctx.set_materialize_grads(False)  # a missing gradient is a zero one below
         ctx.dims = (A, D, y.shape[-1])
         ctx.wacc = wacc
+        ctx.rows = rows  # (handoff.RowBound, level) or None
         return y  # [.., 16]: A logits, 4A deltas, zero padding (_RPNGatherFn splits it)
 
     @staticmethod
@@ -203,6 +221,19 @@ class _RPNHead1x1Fn(torch.autograd.Function):
         A, D, C16 = ctx.dims
         if g16 is None:
             g16 = share.new_zeros(*share.shape[:-1], C16)
+        if ctx.rows is not None:
+            # a zero g16 row is a zero row of the gradient below (the 1x1
+            # dgrad maps row to row, the gate only zeroes more): census it
+            # here, 16 wide, for the shared 3x3's backward -- only under a
+            # bound the loss declared, never inferred from the values
+            bound, level = ctx.rows
+            N, H, W = g16.shape[:3]
+            census = None
+            if bound.wants_census(N, N * H * W) and g16.is_cuda and C16 % 4 == 0:
+                census = ops.row_census(
+                    g16, bound.capacity(N), owner=bound,
+                    dilate=bound.dilate if bound.wants_list(N, N * H * W) else None)
+            bound.publish(level, census)
         gx = None
         if ctx.needs_input_grad[0]:
             # 1x1 stride-1 dgrad: the forward weights' HWIO [1, 1, C, 16] is
@@ -221,7 +252,7 @@ class _RPNHead1x1Fn(torch.autograd.Function):
             # multi-level skinny wgrad at the last (the same sums)
             lv = acc.defer((share, g16))
             if lv is None:
-                return gx, None, None, None, None, None, None, None, None
+                return gx, None, None, None, None, None, None, None, None, None
             if len(lv) <= 8 and all(ops.skinny_levels_ok(x) for x, _ in lv):
                 gw, gb = ops.wgrad_skinny_levels([x for x, _ in lv], [g for _, g in lv])
             else:
@@ -233,10 +264,10 @@ class _RPNHead1x1Fn(torch.autograd.Function):
             out = acc.accumulate(lambda buf: ops.wgrad_skinny(share, g16, with_bias=True,
                                                               accumulate_into=buf))
             if out is None:
-                return gx, None, None, None, None, None, None, None, None
+                return gx, None, None, None, None, None, None, None, None, None
             gw, gb = out
         return (gx, gw[..., :A].contiguous(), gb[:A], gw[..., A:A + D].contiguous(), gb[A:A + D],
-                None, None, None, None)
+                None, None, None, None, None)
 
 
 @PROPOSAL_GENERATOR_REGISTRY.register()
@@ -306,6 +337,13 @@ class RPN(Layer):
                                               self.box2box_transform.weights,
                                               self.smooth_l1_beta,
                                               scale=norm * self.loss_weight)
+            # d2mi_rpn_loss's backward is zero off the sampled anchors, and
+            # subsample_labels keeps at most batch_size_per_image of them per
+            # image: at most that many pixel rows of the head's gradient are
+            # non-zero (the head's backwards may skip the rest)
+            bound = handoff.tagged(pl, handoff.ROW_BOUND)
+            if bound is not None:
+                bound.declare(self.batch_size_per_image)
             return {"loss_rpn_cls": loss_cls, "loss_rpn_loc": loss_loc}
         matched = torch.gather(gt_boxes, 1, matches[..., None].expand(-1, -1, 4))
         gt_deltas = self.box2box_transform.get_deltas(

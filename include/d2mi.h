@@ -114,7 +114,8 @@ int d2mi_set_tuning(const char* key, int value);
 /* Current value of a d2mi_set_tuning key (INT32_MIN for an unknown key). */
 int d2mi_get_tuning(const char* key);
 /* Device int32 error word. Bits: 1 = box_ind out of range (CropAndResize),
- * 2 = NMS segment longer than its declared capacity, 4 = top-k capacity. */
+ * 2 = NMS segment longer than its declared capacity, 4 = top-k capacity,
+ * 8 = more non-zero gradient rows than the declared bound (d2mi_row_census). */
 int32_t* d2mi_error_word_dev(void);
 int d2mi_clear_errors(void* stream);
 /* Node census of a captured, not yet instantiated hipGraph (hipGraph_t as
@@ -628,6 +629,61 @@ int d2mi_conv2d_wgrad_ex(const float* x, const float* dy, float* dw_hwio, float*
                          int H, int W, int Cin, int Cout, int KH, int KW, int stride,
                          int pad_beg, int pad_end, int flags, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* Row census of a sparse gradient map g [N*H*W][C] (C % 4 == 0), for a
+ * gradient whose producer can bound its non-zero rows (the RPN loss: at most
+ * RPN.BATCH_SIZE_PER_IMAGE sampled anchors per image).  Written into the
+ * workspace (d2mi_row_census_workspace_size bytes, the caller keeps it until
+ * its readers have run):
+ *   bitmap    one bit per 32-pixel chunk (bit c % 32 of word c / 32), set iff
+ *             a row of the chunk has a non-zero element.  Bits are compared:
+ *             NaN and Inf count as non-zero, -0.0 as zero;
+ *   word_rows the non-zero rows of each bitmap word's 1024 pixels;
+ *   count     their sum;
+ * and with dilate_k > 0
+ *   rows      the ascending, duplicate-free list of the output rows of a
+ *             dilate_k x dilate_k stride-1 conv over g with dilate_pad leading
+ *             pad whose window holds a non-zero row (inside the image only);
+ *             capacity min(capacity * dilate_k^2, N*H*W) entries (at least 1);
+ *   nrows     their number, clamped to that capacity.
+ * count > capacity (or a list past its capacity) sets bit value 8 of the
+ * device error word: the declared bound was false; nothing is written past a
+ * list's capacity.  d2mi_row_census_layout writes {bitmap byte offset, bitmap
+ * words, word_rows byte offset, count byte offset, nrows byte offset, rows
+ * byte offset (-1 without a list), list capacity} into out[7]. */
+size_t d2mi_row_census_workspace_size(int N, int H, int W, int capacity, int dilate_k);
+int d2mi_row_census_layout(int N, int H, int W, int capacity, int dilate_k, int64_t* out,
+                           int out_len);
+int d2mi_row_census(const float* g, int N, int H, int W, int C, int capacity, int dilate_k,
+                    int dilate_pad, void* workspace, size_t workspace_bytes, void* stream);
+/* d2mi_conv2d_nhwc_gated (gate nullable: then d2mi_conv2d_nhwc_ex without bias,
+ * top-down or relu) over the dilated row list of x's census (d2mi_row_census
+ * with this capacity, dilate_k = KH = KW, dilate_pad = pad_beg): for a
+ * same-size stride-1 conv, every output row that is not listed has an
+ * all-zero window.  The dense plan is kept; where the list's capacity is
+ * below the plan's main-launch rows, that launch becomes a fill of its rows
+ * with epilogue(0) (0.f + residual, zero where the gate is not positive) and
+ * a launch over the listed rows with the same K splits and reduce order; the
+ * plan's tail launch runs dense.  Every element sees the dense kernel's own
+ * product sequence: bit-identical.  Returns 1 when the row-list launch ran,
+ * 0 after the dense call, < 0 on error. */
+int d2mi_conv2d_nhwc_rows(const float* x, const float* w_packed, const float* residual,
+                          const float* gate, float* y, int N, int H, int W, int Cin, int Cout,
+                          int KH, int KW, int stride, int pad_beg, int pad_end, int flags,
+                          const void* census, size_t census_bytes, int capacity, int dilate_k,
+                          int dilate_pad, void* workspace, size_t workspace_bytes, void* stream);
+/* d2mi_conv2d_wgrad_ex with the row census of dy (census: the workspace
+ * d2mi_row_census filled for dy's N x OH x OW rows; a superset bitmap is as
+ * good).  Same plan, same slabs, same reduce; the warp-specialised kernel
+ * walks only the chunks whose bit is set, which for finite x is bit-identical
+ * to the dense call (a skipped chunk adds +-0 to sums that start at +0).
+ * The other kernels ignore the bitmap.  Returns 1 when the bitmap kernel
+ * ran, 0 after a dense launch, < 0 on error. */
+int d2mi_conv2d_wgrad_rows(const float* x, const float* dy, float* dw_hwio, float* dbias, int N,
+                           int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                           int pad_beg, int pad_end, int flags, const void* census,
+                           size_t census_bytes, void* workspace, size_t workspace_bytes,
+                           void* stream);
 
 /* ------------------------------------------------------- FrozenBN fold
  * A frozen BatchNorm (moving statistics; lib/layers/normalization.py:15-119
