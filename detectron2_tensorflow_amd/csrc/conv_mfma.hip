@@ -538,13 +538,8 @@ __global__ __launch_bounds__(256, OCC) void conv_mfma_kernel(ConvArgs a) {
       const_cast<float*>(a.w), 0, a.w_bytes, 0x00020000);
   constexpr uint32_t kOOB = 0x80000000u;
 
-  // Staging registers.  Single-buffered LDS runs a 2-deep prefetch of the
-  // activation tile (k-step kt+2 loads while kt computes and kt+1 waits in
-  // the other set) and a 1-deep prefetch of the weight tile (small and
-  // L2-resident): an activation gather has two compute phases to return, one
-  // phase (~0.6 us at 2 workgroups/CU) being below its loaded latency.
-  // OCC 3 (three workgroups per CU): a 1-deep activation prefetch (fewer VGPRs)
-  float4 ra[OCC >= 3 ? 1 : 2][RA], rb[RB];
+  // Staging registers: a 1-deep prefetch of the activation and the weight tile.
+  float4 ra[RA], rb[RB];
   // channel-chunk-major, tap-minor K order: consecutive k-steps read the
   // same 32 channels at neighbouring pixels (the 3x3 taps), which are still
   // in L2 (tap-major order re-fetched them Cin/32 steps later)
@@ -678,66 +673,43 @@ __global__ __launch_bounds__(256, OCC) void conv_mfma_kernel(ConvArgs a) {
 
   if (kt0 < kt1) {
     if constexpr (DB) {
-      load_a(kt0, ra[0]);
+      load_a(kt0, ra);
       load_b(kt0);
-      store_tile(0, ra[0], rb);
+      store_tile(0, ra, rb);
       __syncthreads();
       int buf = 0;
       for (int kt = kt0; kt < kt1; ++kt) {
         const bool more = kt + 1 < kt1;
         if (more) {
-          load_a(kt + 1, ra[0]);
+          load_a(kt + 1, ra);
           load_b(kt + 1);
         }
         if (kPrioMfma) __builtin_amdgcn_s_setprio(1);
         compute(buf);
         if (kPrioMfma) __builtin_amdgcn_s_setprio(0);
-        if (more) store_tile(buf ^ 1, ra[0], rb);
+        if (more) store_tile(buf ^ 1, ra, rb);
         __syncthreads();
         buf ^= 1;
       }
-    } else if constexpr (OCC >= 3) {
-      load_a(kt0, ra[0]);
+    } else {
+      load_a(kt0, ra);
       load_b(kt0);
-      store_tile(0, ra[0], rb);
+      store_tile(0, ra, rb);
       __syncthreads();
       for (int kt = kt0; kt < kt1; ++kt) {
         const bool more = kt + 1 < kt1;
         if (more && !(kAblate & 1)) {
           load_b(kt + 1);
-          load_a(kt + 1, ra[0]);
+          load_a(kt + 1, ra);
         }
         if (kPrioMfma) __builtin_amdgcn_s_setprio(1);
         if (!(kAblate & 4)) compute(0);
         if (kPrioMfma) __builtin_amdgcn_s_setprio(0);
         __syncthreads();
         if (more) {
-          if (!(kAblate & 2)) store_tile(0, ra[0], rb);
+          if (!(kAblate & 2)) store_tile(0, ra, rb);
           __syncthreads();
         }
-      }
-    } else {
-      // step(kt): activation set F is free (its k-step is in LDS), set X
-      // holds kt + 1.  B(kt+1) is issued before A(kt+2), so the store of
-      // k-step kt+1 leaves only A(kt+2) in flight.
-      auto step = [&](int kt, float4 (&F)[RA], const float4 (&X)[RA]) {  // (OCC 2 only)
-        if (kt + 1 < kt1) load_b(kt + 1);
-        if (kt + 2 < kt1) load_a(kt + 2, F);
-        compute(0);
-        __syncthreads();
-        if (kt + 1 < kt1) {
-          store_tile(0, X, rb);
-          __syncthreads();
-        }
-      };
-      load_a(kt0, ra[0]);
-      load_b(kt0);
-      if (kt0 + 1 < kt1) load_a(kt0 + 1, ra[1]);
-      store_tile(0, ra[0], rb);
-      __syncthreads();
-      for (int kt = kt0; kt < kt1; kt += 2) {
-        step(kt, ra[0], ra[1]);
-        if (kt + 1 < kt1) step(kt + 1, ra[1], ra[0]);
       }
     }
   }
@@ -1574,8 +1546,7 @@ extern "C" int d2mi_conv_pack_weights(const float* w_hwio, int KH, int KW, int C
 }
 
 // The tiled kernel of a plan (conv_plan.h: family, resident workgroups).
-// D2MI_CONV_WS / d2mi_set_tuning("conv_ws", d): the warp-specialised
-// 256x128 split kernel (conv_ws_kernel): 0 off, > 0 on.  r3: a
+// The warp-specialised 256x128 split kernel (conv_ws_kernel): r3: a
 // 16-deep, 3/4-stage read-ahead variant measured bit-identical but slower;
 // r4 removed the other measured-slower A/B forms (stream-K, the in-launch
 // split-K fix-up, the multi-level WS launch, the pre-split-plane kernel) --
@@ -1585,15 +1556,12 @@ extern "C" int d2mi_conv_pack_weights(const float* w_hwio, int KH, int KW, int C
 // f32 and split, large grids and small.
 // ML: the multi-level launches (ConvArgs::nlev > 0).
 template <bool SPLIT, bool ML>
-static void launch_conv(int family, int occ, dim3 grid, hipStream_t st, const ConvArgs& a) {
+static void launch_conv(int family, dim3 grid, hipStream_t st, const ConvArgs& a) {
   if (family == kConvWS256x128) {
     // (LD = 3 does not fit the 128-VGPR budget of 4 waves per SIMD: it spills)
     if constexpr (SPLIT && !ML) hipLaunchKernelGGL((conv_ws_kernel<2>), grid, dim3(1024), 0, st, a);
-  } else if (family == kConv128x128 && occ == 3) {
-    hipLaunchKernelGGL((conv_mfma_kernel<2, 2, 2, 2, false, SPLIT, 3, ML>), grid, dim3(256), 0, st,
-                       a);
   } else if (family == kConv128x128) {
-    hipLaunchKernelGGL((conv_mfma_kernel<2, 2, 2, 2, false, SPLIT, 2, ML>), grid, dim3(256), 0, st,
+    hipLaunchKernelGGL((conv_mfma_kernel<2, 2, 2, 2, false, SPLIT, 3, ML>), grid, dim3(256), 0, st,
                        a);
   } else if (family == kConv128x64) {
     hipLaunchKernelGGL((conv_mfma_kernel<4, 1, 1, 2, true, SPLIT, 2, ML>), grid, dim3(256), 0, st,
@@ -1781,9 +1749,9 @@ static int conv_core(const float* x, const float* w_packed, const float* bias,
     c.partial = l.splits > 1 ? slab : nullptr;
     const dim3 g(l.tiles, l.splits);
     if (p.split3)
-      launch_conv<true, false>(p.family, p.occ, g, st, c);
+      launch_conv<true, false>(p.family, g, st, c);
     else
-      launch_conv<false, false>(p.family, p.occ, g, st, c);
+      launch_conv<false, false>(p.family, g, st, c);
     D2MI_LAUNCH_CHECK();
     if (l.reduce == kReduceNone) return 0;
     // (the float4 form reads bias / top-down / residual / gate as float4s)
@@ -2064,9 +2032,9 @@ extern "C" int d2mi_conv2d_nhwc_levels(const float* const* xs, const int32_t* di
   a.tdH = a.tdW = 1;
   const dim3 grid(p.ntiles, p.splits);
   if (flags & kSplit3)
-    launch_conv<true, true>(p.family, p.occ, grid, as_stream(stream), a);
+    launch_conv<true, true>(p.family, grid, as_stream(stream), a);
   else
-    launch_conv<false, true>(p.family, p.occ, grid, as_stream(stream), a);
+    launch_conv<false, true>(p.family, grid, as_stream(stream), a);
   D2MI_LAUNCH_CHECK();
   if (p.splits > 1) {
     hipLaunchKernelGGL(splitk_reduce_levels_kernel, dim3(p.reduce_grid), dim3(256), 0,

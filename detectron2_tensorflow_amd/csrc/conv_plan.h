@@ -68,30 +68,27 @@ enum ConvFamily {
 enum PlanReduce { kReduceNone = 0, kReduceScalar = 1, kReduceFloat4 = 2 };
 
 // Resident workgroups per CU of a family's kernel: the 128x128 kernel runs
-// three (168 VGPRs, 48 KiB LDS: conv_mfma_kernel<..., OCC = 3>; tuning
-// "conv_occ" = 2 keeps it at two, A/B), the narrower tiles two, the
-// warp-specialised and the streaming kernel one.
+// three (168 VGPRs, 48 KiB LDS: conv_mfma_kernel<..., OCC = 3>), the narrower
+// tiles two, the warp-specialised and the streaming kernel one.
 inline int conv_occ(int family) {
   if (family >= kConvWS256x128) return 1;
-  return family == kConv128x128 && tuning(kTuneConvOcc) != 2 ? 3 : 2;
+  return family == kConv128x128 ? 3 : 2;
 }
 
 // The tile family of a shape.  wide_ok: the 128x128 tile may be used -- its
 // kernels only carry the LDS epilogue (Cout % 4 == 0 and 16-B aligned
 // operands); otherwise 128x64.  split: the split-product math; the
-// warp-specialised 256x128 kernel (tuning "conv_ws") exists only in that
+// warp-specialised 256x128 kernel exists only in that
 // form, and takes the long-K convs (>= 16 k-steps: every 3x3 with Cin >= 64,
 // the 1x1s with Cin >= 512), where its deeper staging pipeline pays; the
 // short-K 1x1s (2-8 k-steps) stay on the 3-per-CU kernel, whose prologue /
 // epilogue overlap across workgroups (tools/ws_ab.py, 16 Mask R-CNN shapes).
-inline int conv_family(int64_t M, int Cout, int KH, int KW, int Cin, bool wide_ok, bool split) {
+inline int conv_family(int Cout, int KH, int KW, int Cin, bool wide_ok, bool split) {
   const int f = Cout <= 32 ? kConv128x32 : (Cout <= 64 || !wide_ok ? kConv128x64 : kConv128x128);
   // tuning "conv_ws_mink": the fewest k-steps that go to the WS kernel (A/B)
-  if (f == kConv128x128 && split && tuning(kTuneConvWS) > 0 &&
+  if (f == kConv128x128 && split &&
       KH * KW * ((Cin + kConvBK - 1) / kConvBK) >= tuning(kTuneConvWSMinK) &&
-      KH * KW <= 32 &&  // (the WS stagers keep a 32-bit tap mask per row)
-      // (tuning "conv_ws_mintiles": the fewest 256x128 tiles that go to the WS kernel, A/B)
-      ((M + 255) / 256) * ((Cout + 127) / 128) >= tuning(kTuneConvWSMinTiles))
+      KH * KW <= 32)  // (the WS stagers keep a 32-bit tap mask per row)
     return kConvWS256x128;
   return f;
 }
@@ -155,7 +152,7 @@ inline int plan_conv(const ConvShape& s, int flags, int operands, size_t workspa
   p.OW = OW;
   p.split3 = split;
   p.lds_epi = Cout % 4 == 0 && aligned && (operands & kOpWsAligned) != 0;
-  p.family = conv_family(M, Cout, s.KH, s.KW, Cin, p.lds_epi != 0, split);
+  p.family = conv_family(Cout, s.KH, s.KW, Cin, p.lds_epi != 0, split);
   p.occ = conv_occ(p.family);
   p.BM = conv_bm(p.family);
   p.BN = conv_bn(p.family);
@@ -283,7 +280,7 @@ inline void plan_conv_levels(const int32_t* dims, int nlev, int Cin, int Cout, i
                              size_t workspace_bytes, int cus, ConvLevelsPlan* out) {
   ConvLevelsPlan p = {};
   p.lds_epi = Cout % 4 == 0 && (operands & kOpAligned) != 0;
-  p.family = conv_family(1, Cout, KH, KW, Cin, p.lds_epi != 0, false);
+  p.family = conv_family(Cout, KH, KW, Cin, p.lds_epi != 0, false);
   p.occ = conv_occ(p.family);
   p.BM = conv_bm(p.family);
   p.BN = conv_bn(p.family);
@@ -323,7 +320,6 @@ enum WgradKernel {
   kWgradSplitOcc3 = 2,  // conv_wgrad_split_kernel<2, 2, 3>
   kWgradWS = 3,         // conv_wgrad_ws_kernel<1>
   kWgradWSInc = 4,      // conv_wgrad_ws_kernel<1, true>
-  kWgradWS2 = 5,        // conv_wgrad_ws_kernel<2>
 };
 struct WgradPlan {
   int kernel, TM, TN, BM, BN, OH, OW, nCi, nCo, ntiles, nchunks, splits, chunks_per_split;
@@ -402,7 +398,7 @@ inline int plan_wgrad(const ConvShape& s, int flags, int operands, size_t worksp
   p.TN = Cout > 64 ? 2 : 1;
   // The warp-specialised kernel (256 x 128 tiles, one workgroup per CU; split
   // products only) takes the KxK convs with Cin % 256 == 0, Cout % 128 == 0
-  // (tuning "wgrad_ws"; tools/ws_ab.py --key wgrad_ws: 3x3 shapes 10-20 %
+  // (3x3 shapes 10-20 %
   // faster, the 1x1s 9 % slower -- their 8 chunks of 32 pixels per split are
   // too short for its prologue).  1x1s (tuning "wgrad_ws1" = the GFLOP
   // threshold; 0 = off): only from ~6 GFLOP up -- the smaller ones have too
@@ -411,8 +407,7 @@ inline int plan_wgrad(const ConvShape& s, int flags, int operands, size_t worksp
   // the 4.4 GFLOP res4 1x1s 7 % slower)
   const bool ws1 = taps == 1 && tuning(kTuneWgradWS1) > 0 &&
                    2.0 * (double)P * (double)Cin * Cout >= tuning(kTuneWgradWS1) * 1e9;
-  const bool ws = split3 && tuning(kTuneWgradWS) > 0 && (taps > 1 || ws1) && Cin % 256 == 0 &&
-                  Cout % 128 == 0;
+  const bool ws = split3 && (taps > 1 || ws1) && Cin % 256 == 0 && Cout % 128 == 0;
   p.BM = ws ? 256 : 64 * p.TM;
   p.BN = 64 * p.TN;
   p.nCi = (Cin + p.BM - 1) / p.BM;
@@ -423,19 +418,15 @@ inline int plan_wgrad(const ConvShape& s, int flags, int operands, size_t worksp
   // LDS).  Measured (tools/conv_ab.py --set wgrad): 3% faster on the FPN p2 3x3
   // (134,400 pixels), slower on everything smaller (the extra pixel splits cost
   // more partial traffic than the occupancy gains), so only pixel counts of
-  // 64k and up take it (tuning "wgrad_occ3_min_p"; "wgrad_occ" = 2 disables it).
-  const bool occ3 = !ws && p.TM == 2 && p.TN == 2 && P >= tuning(kTuneWgradOcc3MinP) &&
-                    tuning(kTuneWgradOcc) != 2;
+  // 64k and up take it (tuning "wgrad_occ3_min_p").
+  const bool occ3 = !ws && p.TM == 2 && p.TN == 2 && P >= tuning(kTuneWgradOcc3MinP);
   // the incremental pixel cursor (conv_wgrad_ws_kernel INC): same-size
   // stride-1 convs whose per-thread runs of 4 pixels and 32-pixel chunk
   // steps wrap at most one row and one image, pixel indices < 2^24
   const bool inc = s.stride == 1 && p.OH == s.H && p.OW == s.W && p.OW >= 4 &&
-                   kWgradKP / p.OW + 1 <= p.OH && P + kWgradKP < (1 << 24) &&
-                   tuning(kTuneWgradInc) > 0;
-  // tuning wgrad_ws: 1 = loads one chunk ahead (no spills), 2 = two chunks
-  // ahead (10 VGPRs of the stagers' ring spill at the 128-VGPR budget)
+                   kWgradKP / p.OW + 1 <= p.OH && P + kWgradKP < (1 << 24);
   p.kernel = !split3 ? kWgradF32
-             : ws    ? (tuning(kTuneWgradWS) >= 2 ? kWgradWS2 : inc ? kWgradWSInc : kWgradWS)
+             : ws    ? (inc ? kWgradWSInc : kWgradWS)
                      : (occ3 ? kWgradSplitOcc3 : kWgradSplit);
   // about one round of resident workgroups (1, 2 or 3 per CU; tuning
   // "wgrad_slots"), each walking >= 16 chunks ("wgrad_minch"), at most 128

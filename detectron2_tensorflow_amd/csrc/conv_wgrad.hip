@@ -910,12 +910,10 @@ static int wgrad_launch(const float* x, const float* dy, float* dw_hwio, float* 
   const FastDiv fhw = make_fastdiv((uint32_t)(a.OH * a.OW)), fw = make_fastdiv((uint32_t)a.OW);
   const int tm = p.TM, tn = p.TN;
   const bool listed = bitmap != nullptr && p.chunks_per_split <= kWgradListCap &&
-                      (p.kernel == kWgradWS2 || p.kernel == kWgradWSInc || p.kernel == kWgradWS);
+                      (p.kernel == kWgradWSInc || p.kernel == kWgradWS);
   a.bitmap = listed ? bitmap : nullptr;
   if (listed)
     hipLaunchKernelGGL((conv_wgrad_ws_kernel<1, false, true>), grid, dim3(1024), 0, st, a, fhw, fw);
-  else if (p.kernel == kWgradWS2)
-    hipLaunchKernelGGL((conv_wgrad_ws_kernel<2>), grid, dim3(1024), 0, st, a, fhw, fw);
   else if (p.kernel == kWgradWSInc)
     hipLaunchKernelGGL((conv_wgrad_ws_kernel<1, true>), grid, dim3(1024), 0, st, a, fhw, fw);
   else if (p.kernel == kWgradWS)

@@ -39,7 +39,7 @@ struct RoiArgs {
   const float* gout;
   int32_t* err;
   int bpb;  // forward: output bins per workgroup (16, 32 or 64)
-  int xcd_remap;  // forward: ROIs spread XCD-contiguously (roi_fwd tuning bit 8)
+  int xcd_remap;  // forward: ROIs spread XCD-contiguously
   // backward over one or two ROI sets of the same maps (Contrib::set picks):
   // each set's grad_out and its sampling ratio (the avg-pool divisor)
   const float* gout_s[2];
@@ -159,18 +159,7 @@ constexpr int kMaxBinsPerBlock = 64, kMinBinsPerBlock = 16, kFwdMinBlocks = 2048
 // the L2 the feature maps are being gathered through); XCD: ROI r taken from
 // a bijective XCD-contiguous remap of blockIdx.x (ROIs that neighbour in the
 // sampled layout -- foreground proposals of one GT -- share an XCD's L2).
-template <bool NTL>
-__device__ __forceinline__ float4 ld_row4(const float4* p) {
-  if constexpr (NTL) {
-    typedef float f4v __attribute__((ext_vector_type(4)));
-    const f4v v = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-  } else {
-    return *p;
-  }
-}
-
-template <bool VEC4, int U = 4, bool NT = false, bool NTL = false>
+template <bool VEC4, int U = 4, bool NT = false>
 __global__ __launch_bounds__(256) void roi_align_fwd_kernel(RoiArgs a) {
   int r = blockIdx.x;
   if (a.xcd_remap) {
@@ -210,10 +199,10 @@ __global__ __launch_bounds__(256) void roi_align_fwd_kernel(RoiArgs a) {
         ok[u] = g.ok && ty.valid && tx.valid;
         ly[u] = ty.lerp;
         lx[u] = tx.lerp;
-        c00[u] = ld_row4<NTL>(p + ((size_t)ty.r0 * g.W + tx.r0) * 64 + lane);
-        c01[u] = ld_row4<NTL>(p + ((size_t)ty.r0 * g.W + tx.r1) * 64 + lane);
-        c10[u] = ld_row4<NTL>(p + ((size_t)ty.r1 * g.W + tx.r0) * 64 + lane);
-        c11[u] = ld_row4<NTL>(p + ((size_t)ty.r1 * g.W + tx.r1) * 64 + lane);
+        c00[u] = p[((size_t)ty.r0 * g.W + tx.r0) * 64 + lane];
+        c01[u] = p[((size_t)ty.r0 * g.W + tx.r1) * 64 + lane];
+        c10[u] = p[((size_t)ty.r1 * g.W + tx.r0) * 64 + lane];
+        c11[u] = p[((size_t)ty.r1 * g.W + tx.r1) * 64 + lane];
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -983,118 +972,6 @@ __global__ __launch_bounds__(256) void roi_bwd_pixel_kernel(
   }
 }
 
-// r4 form of roi_bwd_pixel_c256_kernel (tuning "roi_bwd_rec" = 0, A/B): the
-// run's slots ordered in LDS, then a record and a row per contribution.
-// C == 256 form of roi_bwd_pixel_kernel: a wave sums FOUR touched pixels at
-// once, 16 lanes per pixel, 16 channels (4 float4) per lane -- four
-// independent load chains (run bounds -> slots -> records -> grad_out rows)
-// in flight per wave instead of one, the same per-pixel order and rounding.
-template <int PPW>
-__global__ __launch_bounds__(256) void roi_bwd_pixel_c256_slots_kernel(
-    RoiArgs a, PixMap pm, const int32_t* __restrict__ arrival, const Contrib* __restrict__ rec,
-    int set_bits, const int32_t* __restrict__ count, const int32_t* __restrict__ run_start,
-    const int32_t* __restrict__ seg_first, const float* __restrict__ partial,
-    const int32_t* __restrict__ touched, const BwdCounters* __restrict__ ctr, int lv_lo,
-    int lv_hi) {
-  constexpr int C = 256;
-  constexpr int LPP = 64 / PPW;     // lanes per pixel
-  constexpr int F = C / LPP / 4;    // float4 per lane
-  __shared__ int32_t lds[4][PPW][2][kSeg];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int grp = lane / LPP, sub = lane % LPP;
-  const int c = sub * 4 * F;  // this lane's channels
-  TouchedRange tr;
-  tr.init(pm, ctr, lv_lo, lv_hi);
-  const int nt = tr.total();
-  const int nsets = 1 << set_bits;
-  int32_t* lin = lds[w][grp][0];
-  int32_t* lout = lds[w][grp][1];
-  const int wave = blockIdx.x * 4 + w;
-  for (int tb = wave * PPW; tb < nt; tb += gridDim.x * 4 * PPW) {
-    const int t = tb + grp;
-    if (t >= nt) continue;
-    int l;
-    const long long pix = tr.at(pm, touched, t, l);
-    float* dst = a.gfeat[l] + (size_t)(pix - pm.base[l]) * C + c;
-    float4* d4 = reinterpret_cast<float4*>(dst);
-    // accumulate: the map's old value is loaded first, its latency hidden
-    // behind the contribution sums (r4: the deferred per-level passes into
-    // the RPN head's dgrad output waited on it at the end)
-    const bool acc_lv = (a.acc_mask >> l) & 1;
-    float4 old[F];
-    if (acc_lv) {
-#pragma unroll
-      for (int k = 0; k < F; ++k) old[k] = d4[k];
-    }
-    float4 res[F];
-    bool any = false;
-    for (int sidx = 0; sidx < nsets; ++sidx) {
-      const long long q = (pix << set_bits) | sidx;
-      const int n = count[q];
-      if (n == 0) continue;
-      const int i0 = run_start[q];
-      float4 acc[F];
-#pragma unroll
-      for (int k = 0; k < F; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (n <= kSeg) {
-        order_run<LPP>(arrival, i0, n, sub, lin, lout);
-        for (int i = 0; i < n; ++i) {
-          const int slot = lout[i];
-          const int corner = slot & 3;
-          const Contrib e = rec[slot >> 2];
-          const float4* src =
-              reinterpret_cast<const float4*>(a.gout_s[e.set] + (size_t)e.row * C + c);
-          float4 v[F];
-#pragma unroll
-          for (int k = 0; k < F; ++k) v[k] = src[k];
-          const int sr = a.sr_s[e.set];
-          const BinDiv bd = bin_div(sr);
-#pragma unroll
-          for (int k = 0; k < F; ++k) {
-            float4 g = v[k];
-            if (sr > 0) g = div4(g, bd);
-            acc[k].x += weigh(corner, e.yl, e.xl, g.x);
-            acc[k].y += weigh(corner, e.yl, e.xl, g.y);
-            acc[k].z += weigh(corner, e.yl, e.xl, g.z);
-            acc[k].w += weigh(corner, e.yl, e.xl, g.w);
-          }
-        }
-      } else {
-        const int f = seg_first[q];
-        const int ns = (n + kSeg - 1) / kSeg;
-        for (int j = 0; j < ns; ++j) {
-          const float4* src = reinterpret_cast<const float4*>(partial + (size_t)(f + j) * C + c);
-#pragma unroll
-          for (int k = 0; k < F; ++k) {
-            const float4 v = src[k];
-            acc[k].x += v.x; acc[k].y += v.y; acc[k].z += v.z; acc[k].w += v.w;
-          }
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < F; ++k) {
-        if (any) {
-          res[k].x = res[k].x + acc[k].x; res[k].y = res[k].y + acc[k].y;
-          res[k].z = res[k].z + acc[k].z; res[k].w = res[k].w + acc[k].w;
-        } else {
-          res[k] = acc[k];
-        }
-      }
-      any = true;
-    }
-    if (!any) continue;
-#pragma unroll
-    for (int k = 0; k < F; ++k) {
-      if (acc_lv) {
-        const float4 o = old[k];
-        res[k].x = o.x + res[k].x; res[k].y = o.y + res[k].y;
-        res[k].z = o.z + res[k].z; res[k].w = o.w + res[k].w;
-      }
-      d4[k] = res[k];
-    }
-  }
-}
-
 // C == 256 form of roi_bwd_pixel_kernel: a wave sums PPW touched pixels at
 // once, 64 / PPW lanes per pixel -- PPW independent load chains (run bounds
 // -> run records -> grad_out rows) in flight per wave instead of one, the
@@ -1115,12 +992,12 @@ __global__ __launch_bounds__(256) void roi_bwd_pixel_c256_slots_kernel(
 // (profiles/r5_roi_ppw2_timed_kernel_stats.csv), in-step -0.43 %
 // (profiles/r5_ab_roi_ppw2_rb4.log); one pixel per wave with 8 rows and two
 // with 2 rows measured the same (r5_ab_roi_ppw1_vs_ppw2.log, _rb2_vs_rb4.log).
-template <int PPW, int kRowBatch>
 __global__ __launch_bounds__(256) void roi_bwd_pixel_c256_kernel(
     RoiArgs a, PixMap pm, const RunRec* __restrict__ runrec, int set_bits,
     const int4* __restrict__ trun, const float* __restrict__ partial,
     const BwdCounters* __restrict__ ctr, int lv_lo, int lv_hi) {
   constexpr int C = 256;
+  constexpr int PPW = 2, kRowBatch = 4;  // pixels per wave, rows in flight per lane
   constexpr int LPP = 64 / PPW;     // lanes per pixel
   constexpr int F = C / LPP / 4;    // float4 per lane
   constexpr int KR = kSeg / LPP;    // run records per lane
@@ -1327,42 +1204,23 @@ extern "C" int d2mi_roi_align_fwd(const float* const* feats, const int32_t* dims
   while (a.bpb > kMinBinsPerBlock &&
          (long long)R * ((nbins + a.bpb - 1) / a.bpb) < kFwdMinBlocks)
     a.bpb /= 2;
-  // tuning "roi_fwd" (A/B, tools/roi_ab.py): bit 1 = 2 bins per wave
-  // iteration (fewer VGPRs, more resident waves), bit 2 = the blocks of a ROI
-  // split its bins evenly, bit 4 = non-temporal output stores, bit 8 = XCD-
-  // contiguous ROI order.  Default (-1): 2 | 4 | 8, and 1 from 256 ROIs up --
-  // measured on the training step's own ROIs: the box pooler (1,024 ROIs)
+  // The blocks of a ROI split its bins evenly, the output stores are
+  // non-temporal, the ROIs are taken in XCD-contiguous order, and from 256
+  // ROIs up a wave iteration takes 2 bins (fewer VGPRs, more resident waves)
+  // -- measured on the training step's own ROIs: the box pooler (1,024 ROIs)
   // 32.1 -> 26.3 us (XCD order alone 28.1: ROIs that neighbour in the sampled
   // layout share an L2), the mask pooler (32 ROIs x 14x14) 19.7 -> 18.9-19.6
-  int tv = tuning(kTuneRoiFwd);
-  if (tv < 0) tv = 2 | 4 | 8 | (R >= 256 ? 1 : 0);
-  // r6, bit 16: ONE wave iteration per wave -- a workgroup takes 4 x U bins,
-  // so every wave issues all of its corner loads in one round (the bins'
-  // loads no longer wait on the previous bins' round trips); bit 32: U = 8
-  const int U = (tv & 32) ? 8 : (tv & 1) ? 2 : 4;
-  if (tv & 16) a.bpb = 4 * U;
   const int nby = (nbins + a.bpb - 1) / a.bpb;
-  if (tv & 2) a.bpb = (nbins + nby - 1) / nby;
-  a.xcd_remap = (tv & 8) ? 1 : 0;
+  a.bpb = (nbins + nby - 1) / nby;
+  a.xcd_remap = 1;
   dim3 grid(R, nby);
   hipStream_t st = as_stream(stream);
   if (!vec4)
     hipLaunchKernelGGL((roi_align_fwd_kernel<false>), grid, dim3(256), 0, st, a);
-  else if (tv & 64) {  // r6, bit 64: the corner rows loaded non-temporally
-    if (U == 2)
-      hipLaunchKernelGGL((roi_align_fwd_kernel<true, 2, true, true>), grid, dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((roi_align_fwd_kernel<true, 4, true, true>), grid, dim3(256), 0, st, a);
-  } else if (U == 8)
-    hipLaunchKernelGGL((roi_align_fwd_kernel<true, 8, true>), grid, dim3(256), 0, st, a);
-  else if ((tv & 5) == 0)
-    hipLaunchKernelGGL((roi_align_fwd_kernel<true, 4, false>), grid, dim3(256), 0, st, a);
-  else if ((tv & 5) == 1)
-    hipLaunchKernelGGL((roi_align_fwd_kernel<true, 2, false>), grid, dim3(256), 0, st, a);
-  else if ((tv & 5) == 4)
-    hipLaunchKernelGGL((roi_align_fwd_kernel<true, 4, true>), grid, dim3(256), 0, st, a);
-  else
+  else if (R >= 256)
     hipLaunchKernelGGL((roi_align_fwd_kernel<true, 2, true>), grid, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((roi_align_fwd_kernel<true, 4, true>), grid, dim3(256), 0, st, a);
   D2MI_LAUNCH_CHECK();
   return 0;
 }
@@ -1479,10 +1337,8 @@ int roi_bwd_core(const RoiArgs* sets, int nsets, const int32_t* dims, int num_le
   D2MI_REQUIRE(w.ok() && (workspace || w.off == 0),
                "ROIAlign backward workspace too small: %zu < %zu", workspace_bytes, w.off);
   if (p.total_pixels == 0) return 0;
-  // r5: the C = 256 pixel pass reads run records (tuning "roi_bwd_rec", 1);
-  // 0 = the r4 slot pass (A/B).  Phase 1 and phase 2 of one backward must
-  // see the same value (a deferred pass reads what the prepare wrote).
-  const bool use_runrec = vec4 && C == 256 && tuning(kTuneRoiBwdRec) != 0;
+  // the C = 256 pixel pass reads run records
+  const bool use_runrec = vec4 && C == 256;
   if (phase & 1) {
   ClearList cl = {};
   long long clear_words = 0;
@@ -1557,34 +1413,10 @@ int roi_bwd_core(const RoiArgs* sets, int nsets, const int32_t* dims, int num_le
   const long long cap = p.pm.tbase[lv_hi + 1] - p.pm.tbase[lv_lo];
   const long long wg_max = std::max(1, tuning(kTuneRoiPixGrid));
   const dim3 grid((unsigned)std::max(1LL, std::min((cap + 3) / 4, wg_max)));
-  if (vec4 && C == 256) {
-    const int ppw = tuning(kTuneRoiBwdPpw);
-    // tuning "roi_bwd_rec" (the run-record pass): 1 two pixels per wave, 4
-    // rows in flight per lane (r5c, default); 2 / 3 four pixels per wave with
-    // 2 / 4 rows (r5b: 4); 5 one pixel per wave, 8 rows; tuning "roi_bwd_ppw" = 8
-    // eight pixels per wave (A/B forms)
-    const int tv = tuning(kTuneRoiBwdRec);
-    const int pw = ppw == 8 ? 8 : tv == 5 ? 1 : (tv == 2 || tv == 3) ? 4 : 2;  // pixels per wave
-    const dim3 g4((unsigned)std::max(1LL, std::min((cap + 4 * pw - 1) / (4 * pw), wg_max)));
-    if (!use_runrec)  // the r4 pixel pass (A/B)
-      hipLaunchKernelGGL(roi_bwd_pixel_c256_slots_kernel<4>, g4, dim3(256), 0, st, a, p.pm,
-                         s.arrival, s.rec, sb, s.count, s.run_start, s.seg_first, s.partial,
-                         s.touched, s.ctr, lv_lo, lv_hi);
-    else if (ppw == 8)
-      hipLaunchKernelGGL((roi_bwd_pixel_c256_kernel<8, 4>), g4, dim3(256), 0, st, a, p.pm, s.runrec,
-                         sb, s.trun, s.partial, s.ctr, lv_lo, lv_hi);
-    else if (tv == 2)
-      hipLaunchKernelGGL((roi_bwd_pixel_c256_kernel<4, 2>), g4, dim3(256), 0, st, a, p.pm, s.runrec,
-                         sb, s.trun, s.partial, s.ctr, lv_lo, lv_hi);
-    else if (tv == 3)
-      hipLaunchKernelGGL((roi_bwd_pixel_c256_kernel<4, 4>), g4, dim3(256), 0, st, a, p.pm, s.runrec,
-                         sb, s.trun, s.partial, s.ctr, lv_lo, lv_hi);
-    else if (tv == 5)
-      hipLaunchKernelGGL((roi_bwd_pixel_c256_kernel<1, 8>), g4, dim3(256), 0, st, a, p.pm, s.runrec,
-                         sb, s.trun, s.partial, s.ctr, lv_lo, lv_hi);
-    else
-      hipLaunchKernelGGL((roi_bwd_pixel_c256_kernel<2, 4>), g4, dim3(256), 0, st, a, p.pm, s.runrec,
-                         sb, s.trun, s.partial, s.ctr, lv_lo, lv_hi);
+  if (use_runrec) {  // two pixels per wave
+    const dim3 g4((unsigned)std::max(1LL, std::min((cap + 7) / 8, wg_max)));
+    hipLaunchKernelGGL(roi_bwd_pixel_c256_kernel, g4, dim3(256), 0, st, a, p.pm, s.runrec, sb,
+                       s.trun, s.partial, s.ctr, lv_lo, lv_hi);
   } else if (vec4) {
     hipLaunchKernelGGL(roi_bwd_pixel_kernel<true>, grid, dim3(256), 0, st, a, p.pm, s.arrival,
                        s.rec, sb, s.count, s.run_start, s.seg_first, s.partial, s.touched, s.ctr,

@@ -405,7 +405,7 @@ __device__ __forceinline__ v4i expand16(uint32_t x) {
   return r;
 }
 
-// The same by table (r6): an LDS table of the 256 byte values' 8-byte
+// The same by table: an LDS table of the 256 byte values' 8-byte
 // expansions, two lookups per 16 bits (4 VALU + 2 LDS reads instead of 12 VALU)
 __device__ __forceinline__ v4i expand16_lut(uint32_t x, const uint2* __restrict__ lut) {
   const uint2 lo = lut[x & 0xFFu], hi = lut[(x >> 8) & 0xFFu];
@@ -435,19 +435,16 @@ __device__ __forceinline__ void tri_pair(int u, int T, int& ti, int& tj) {
 // partial tile per workgroup goes to the workspace.
 constexpr int kIWaves = 8;
 
-template <bool LUT>
 __global__ __launch_bounds__(64 * kIWaves) void solo_inter_mfma_kernel(
     const uint64_t* __restrict__ bits, int N, int k, int W64, int T, int groups,
     int words_per_wave, int32_t* __restrict__ part, float* __restrict__ comp) {
   extern __shared__ __align__(16) unsigned char ism[];
   __shared__ uint2 lut[256];
-  if (LUT) {
-    for (int v = threadIdx.x; v < 256; v += 64 * kIWaves) {
-      const v4i e = expand16((uint32_t)v);
-      lut[v] = make_uint2((uint32_t)e[0], (uint32_t)e[1]);
-    }
-    __syncthreads();
+  for (int v = threadIdx.x; v < 256; v += 64 * kIWaves) {
+    const v4i e = expand16((uint32_t)v);
+    lut[v] = make_uint2((uint32_t)e[0], (uint32_t)e[1]);
   }
+  __syncthreads();
   if (blockIdx.x == 0)  // (the reduce launch max-folds the compensation into it)
     for (int e = threadIdx.x; e < N * k; e += 64 * kIWaves) comp[e] = 0.f;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -504,8 +501,7 @@ __global__ __launch_bounds__(64 * kIWaves) void solo_inter_mfma_kernel(
         v4i fr[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-          fr[q] = LUT ? expand16_lut((uint32_t)(d[q] >> (32 * half32 + 16 * h)) & 0xFFFFu, lut)
-                      : expand16((uint32_t)(d[q] >> (32 * half32 + 16 * h)) & 0xFFFFu);
+          fr[q] = expand16_lut((uint32_t)(d[q] >> (32 * half32 + 16 * h)) & 0xFFFFu, lut);
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -1157,15 +1153,8 @@ extern "C" int d2mi_solo_matrix_nms(const uint64_t* mask_bits, const int64_t* cl
     const int T = (k + kIT - 1) / kIT, tri = T * (T + 1) / 2;
     const int slices = groups * kIWaves;
     const int wpw = ((W64 + slices - 1) / slices + kIWords - 1) / kIWords * kIWords;
-    // tuning "solo_mfma": 2 (default) = bits expanded by an LDS table (r6:
-    // intersections 38.1 -> 31.9 us per call, profiles/r6m_stats_*.csv), 1 = by
-    // arithmetic
-    if (tuning(kTuneSoloMfma) == 2)
-      hipLaunchKernelGGL(solo_inter_mfma_kernel<true>, dim3(N * tri * groups), dim3(64 * kIWaves),
-                         kIWaves * kIWaveB, st, mask_bits, N, k, W64, T, groups, wpw, part, comp);
-    else
-      hipLaunchKernelGGL(solo_inter_mfma_kernel<false>, dim3(N * tri * groups), dim3(64 * kIWaves),
-                         kIWaves * kIWaveB, st, mask_bits, N, k, W64, T, groups, wpw, part, comp);
+    hipLaunchKernelGGL(solo_inter_mfma_kernel, dim3(N * tri * groups), dim3(64 * kIWaves),
+                       kIWaves * kIWaveB, st, mask_bits, N, k, W64, T, groups, wpw, part, comp);
     D2MI_LAUNCH_CHECK();
     hipLaunchKernelGGL(solo_inter_reduce_kernel<kIT>, dim3(N * tri * (kIT / kRedCols)), dim3(256), 0,
                        st, part, N, k, T, groups, sum_masks, classes, iouT, comp);

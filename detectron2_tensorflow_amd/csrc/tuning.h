@@ -10,39 +10,32 @@ namespace d2mi {
 // environment variable is D2MI_<key in capitals>.
 // defaults: measured per shape and in the training step
 // conv_stream: the streaming 1x1 for launches of >= 8192 output pixels (r5 in-step A/B:
-// -0.85 %, profiles/r5_ab_inproc_conv_stream.log); roi_bwd_rec: run records (-0.41 %);
+// -0.85 %, profiles/r5_ab_inproc_conv_stream.log);
 // retina_fused: RetinaNet inference in four launches (retina_post.hip; 0 the
 // unfused pipeline, 2 the fused one with its in-workgroup exact select forced)
 // rpn_merge: the RPN's per-image concat + top-k as a merge rank (proposals.hip)
-// solo_mfma: the SOLOv2 Matrix-NMS intersections on int8 MFMA (solo.hip, r6):
-// 2 = bits expanded by an LDS table (default), 1 = by arithmetic, 0 = the AND +
-// popcount tiles; retina_var: the r6 RetinaNet post (compaction, early
+// solo_mfma: the SOLOv2 Matrix-NMS intersections on int8 MFMA, bits expanded
+// by an LDS table (solo.hip); 0 = the AND + popcount tiles;
+// retina_var: the r6 RetinaNet post (compaction, early
 // select bound, DPP / permlane bitonic and select, NMS IoU only where boxes
 // meet, NMS tiles resolved as a ballot fixed point, the floor's radix select,
 // the rank launch's rounds looped, small levels' floor samples spread over the
 // level: 12018; 0 = the r5 form; + 4096, the rank
 // inside the NMS per 128-candidate window, is faster on iid logits and slower
 // on a model's head outputs, where the NMS needs several windows)
-// conv_occ / wgrad_occ: 2 keeps the 128x128 conv / split wgrad kernels at two
-// workgroups per CU; conv_split_slots / wgrad_slots: the split-K / pixel-split
+// conv_split_slots / wgrad_slots: the split-K / pixel-split
 // workgroup target (0: the plan's own); conv_tail: 0 no tail split;
 // wgrad_occ3_min_p: the pixel count from which the 3-per-CU wgrad runs;
 // wgrad_minch / wgrad_maxsplit: fewest chunks per split / most splits (<= 0:
-// the default); wgrad_prio: MFMA wave priority; roi_bwd_ppw: 8 = eight pixels
-// per wave in the ROIAlign backward pixel pass; topk_floor: 0 = radix passes only
+// the default); wgrad_prio: MFMA wave priority; topk_floor: 0 = radix passes only
 #define D2MI_TUNE_KNOBS(X)                       \
-  X(kTuneConvWS, "conv_ws", 2)                   \
-  X(kTuneRoiFwd, "roi_fwd", -1)                  \
-  X(kTuneWgradWS, "wgrad_ws", 1)                 \
   X(kTuneConvEpi, "conv_epi", 1)                 \
   X(kTuneWgradWS1, "wgrad_ws1", 6)               \
   X(kTuneWgradXCD, "wgrad_xcd", 1)               \
   X(kTuneConvXCD, "conv_xcd", 1)                 \
-  X(kTuneWgradInc, "wgrad_inc", 1)               \
   X(kTuneConvWSMinK, "conv_ws_mink", 16)         \
   X(kTuneRoiPixGrid, "roi_pix_grid", 8192)       \
   X(kTuneConvStream, "conv_stream", 8192)        \
-  X(kTuneRoiBwdRec, "roi_bwd_rec", 1)            \
   X(kTuneRetinaFused, "retina_fused", 1)         \
   X(kTuneRpnMerge, "rpn_merge", 1)               \
   X(kTuneNmsScan, "nms_scan", 1)                 \
@@ -51,21 +44,17 @@ namespace d2mi {
   X(kTuneConvStreamNt, "conv_stream_nt", 2)      \
   X(kTuneConvNt, "conv_nt", 0)                   \
   X(kTuneConvTailMinK, "conv_tail_mink", 8)      \
-  X(kTuneConvWSMinTiles, "conv_ws_mintiles", 0)  \
   X(kTuneSgdRev, "sgd_rev", 0)                   \
   X(kTuneRetinaRank, "retina_rank", 0)           \
   X(kTuneSoloMfma, "solo_mfma", 2)               \
   X(kTuneRetinaVar, "retina_var", 12018)         \
-  X(kTuneConvOcc, "conv_occ", 3)                 \
   X(kTuneConvSplitSlots, "conv_split_slots", 0)  \
   X(kTuneConvTail, "conv_tail", 1)               \
-  X(kTuneWgradOcc, "wgrad_occ", 3)               \
   X(kTuneWgradOcc3MinP, "wgrad_occ3_min_p", 65536) \
   X(kTuneWgradSlots, "wgrad_slots", 0)           \
   X(kTuneWgradMinCh, "wgrad_minch", 16)          \
   X(kTuneWgradMaxSplit, "wgrad_maxsplit", 128)   \
   X(kTuneWgradPrio, "wgrad_prio", 1)             \
-  X(kTuneRoiBwdPpw, "roi_bwd_ppw", 0)            \
   X(kTuneTopkFloor, "topk_floor", 1)
 enum TuneKey {
 #define X(id, key, def) id,

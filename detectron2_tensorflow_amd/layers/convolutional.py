@@ -16,7 +16,6 @@ wgrad on the MFMA wgrad kernel or hipBLASLt / MIOpen, whichever measured
 faster for the shape (see _wgrad); stride-2 KxK dgrad and Cout % 4 != 0 use
 torch.nn.grad.
 """
-import os
 
 import torch
 import torch.nn.functional as F
@@ -86,7 +85,7 @@ def _dgrad(gy, w, x_shape, stride, pb, pe, relu_gate=None, add=None, add2=None, 
     return gx if add is None else gx + add
 
 
-_WGRAD_1X1_MIN_P = int(os.environ.get("D2MI_WGRAD_1X1_MIN_P", "8192"))
+_WGRAD_1X1_MIN_P = 8192
 
 
 def _wgrad(x, gy, w_shape, stride, pb, pe, want_bias=False, accumulate_into=None, census=None):

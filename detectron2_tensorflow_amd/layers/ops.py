@@ -522,9 +522,8 @@ def subsample(labels, num_samples, num_pos, bg_label, seed, order_slots=0):
 
 
 # The ROI heads' label / take / mask-prep glue on d2mi_roi_gt_classes and
-# d2mi_roi_sample_take (False: torch's gathers, selects, argsort; tests compare;
-# D2MI_FUSED_SAMPLE_TAKE=0 for a bench A/B).
-FUSED_SAMPLE_TAKE = os.environ.get("D2MI_FUSED_SAMPLE_TAKE", "1") != "0"
+# d2mi_roi_sample_take (False: torch's gathers, selects, argsort; tests compare).
+FUSED_SAMPLE_TAKE = True
 
 
 def roi_gt_classes(labels, matches, gt_classes, pvalid, num_classes):
@@ -674,13 +673,6 @@ def split_bf16x3(x):
 _CONV_WS, _WGRAD_WS = {}, {}
 
 
-# Narrow-Cout convs (<= 64: the 128x64 / 128x32 tiles) run the split-product
-# kernel too (r2 A/B, tools/conv_ab.py: res2 3x3 64->64 125 -> 103 us, 1x1
-# 256->64 71 -> 61 us, 512->64 46 -> 34 us vs the native f32 MFMA);
-# D2MI_NARROW_SPLIT=0 puts them back on the f32 kernel.
-_NARROW_SPLIT = os.environ.get("D2MI_NARROW_SPLIT", "1") != "0"
-
-
 def conv2d_nhwc(x, w_packed, bias=None, stride=1, pad=(0, 0), relu=False, topdown=None,
                 residual=None, relu_after_add=False, math_mode=None, flip_taps=False,
                 relu_gate=None, out=None, census=None):
@@ -730,8 +722,6 @@ def conv2d_nhwc(x, w_packed, bias=None, stride=1, pad=(0, 0), relu=False, topdow
             raise ValueError(f"relu_gate {tuple(relu_gate.shape)} != output {tuple(y.shape)}")
     if residual is not None and residual.shape != y.shape:
         raise ValueError(f"residual {tuple(residual.shape)} != output {tuple(y.shape)}")
-    if math_mode == "split" and Cout <= 64 and not _NARROW_SPLIT:
-        math_mode = "f32"
     flags = (1 if relu else 0) | (2 if relu_after_add else 0) | (8 if flip_taps else 0)
     if math_mode == "split":
         flags |= 4
@@ -834,8 +824,6 @@ def conv2d_nhwc_levels(xs, w_packed, bias=None, stride=1, pad=(0, 0), relu=False
         OW = (W + pb + pe - KW) // stride + 1
         ys.append(torch.empty((N, OH, OW, Cout), dtype=torch.float32, device=x.device))
         dims += [N, H, W]
-    if math_mode == "split" and Cout <= 64 and not _NARROW_SPLIT:
-        math_mode = "f32"
     flags = (1 if relu else 0) | (4 if math_mode == "split" else 0)
     xp = _C.host_array(_C.c_void_p, [x.data_ptr() for x in xs])
     yp = _C.host_array(_C.c_void_p, [y.data_ptr() for y in ys])
@@ -1019,7 +1007,7 @@ OP_TOPDOWN, OP_RESIDUAL, OP_GATE, OP_ALIGNED, OP_BIAS_ALIGNED, OP_WORKSPACE, OP_
     1, 2, 4, 8, 16, 32, 64)
 OP_ALL_ALIGNED = OP_ALIGNED | OP_BIAS_ALIGNED | OP_WS_ALIGNED
 CONV_FAMILIES = ("tiled128x128", "tiled128x64", "tiled128x32", "ws256x128", "stream1x1")
-WGRAD_KERNELS = ("f32", "split", "split_occ3", "ws", "ws_inc", "ws2")
+WGRAD_KERNELS = ("f32", "split", "split_occ3", "ws", "ws_inc")
 _LAUNCH_FIELDS = ("tile0", "tiles", "splits", "kt_per_split", "m_base", "m_end", "reduce",
                   "reduce_grid")
 CONV_PLAN_FIELDS = (("family", "occ", "split3", "lds_epi", "M", "BM", "BN", "nM", "nN", "nk")
@@ -1489,9 +1477,8 @@ def stem_conv(x, w3):
 
 
 # Device images preprocessed by d2mi_preprocess_images (False: torch's
-# subtract / divide / flip / pad, five launches; tests compare;
-# D2MI_FUSED_PREPROCESS=0 for a bench A/B).
-FUSED_PREPROCESS = os.environ.get("D2MI_FUSED_PREPROCESS", "1") != "0"
+# subtract / divide / flip / pad, five launches; tests compare).
+FUSED_PREPROCESS = True
 
 
 def preprocess_images(x, mean, std, flip, size_divisibility=0):

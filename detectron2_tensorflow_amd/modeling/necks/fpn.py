@@ -8,7 +8,6 @@ LastLevelMaxPool is max_pool k1/s2 = p5[:, ::2, ::2] (fpn.py:171-183);
 LastLevelP6P7 returns post-ReLU p6 and p7 = conv3x3/2(p6) (fpn.py:186-217).
 """
 import math
-import os
 
 import torch
 
@@ -100,7 +99,7 @@ class FPN(Layer):
     # joins that pair's gradient hand-off, so the last of the three backwards
     # forms the feature's whole gradient with its ReLU mask (no autograd add,
     # no threshold pass; the join of layers/handoff.py).
-    JOIN_GRAD = os.environ.get("D2MI_FPN_JOIN", "1") != "0"
+    JOIN_GRAD = True
 
     def _join_of(self, name, feats):
         if not self.JOIN_GRAD:
@@ -113,7 +112,7 @@ class FPN(Layer):
     # next finer lateral: the two backwards hand its gradient over (the second
     # adds it; the output conv inside its dgrad epilogue) instead of an
     # autograd add of two full maps (the top-down Pair of layers/handoff.py).
-    TD_HANDOFF = os.environ.get("D2MI_FPN_TD", "1") != "0"
+    TD_HANDOFF = True
 
     def _out(self, out, prev, fused):
         if not (fused and self.TD_HANDOFF and torch.is_grad_enabled() and prev.requires_grad):

@@ -46,22 +46,14 @@ const char* d2mi_last_error(void);
 /* Process-wide kernel-selection knobs for in-process A/B timing (tools/);
  * each starts from its environment variable (D2MI_<KEY in capitals>).  No
  * reference counterpart (a tuning hook of this implementation).  Keys:
- *   "conv_ws"      warp-specialised 256x128 split conv for the long-K convs:
- *                  0 off, else on (default 2);
- *   "roi_fwd"      ROIAlign forward variant bits (-1 = default);
- *   "wgrad_ws"     warp-specialised split weight gradient for KxK convs
- *                  (Cin % 256 == 0, Cout % 128 == 0): 0 off, 1 (default) on;
  *   "conv_epi"     split-K partials stored from the accumulators (1, default)
  *                  or through the LDS epilogue (0);
  *   "wgrad_ws1"    the WS weight gradient on 1x1 convs of >= N GFLOP (6);
  *   "wgrad_xcd" / "conv_xcd"  XCD-contiguous grid remaps (1 on);
- *   "wgrad_inc"    incremental pixel cursor in the WS weight gradient (1 on);
  *   "conv_ws_mink" fewest k-steps that go to the WS conv (16);
  *   "roi_pix_grid" ROIAlign backward pixel-pass grid (8192);
  *   "conv_stream"  streaming short-K 1x1 conv (r5) for stride-1 1x1 launches
  *                  of at least this many output pixels; 0 = off;
- *   "roi_bwd_rec"  ROIAlign backward pixel pass over run records (r5, 1) or
- *                  the r4 slot pass (0); 2 / 3 / 5 other pixel x record shapes;
  *   "retina_fused" RetinaNet post-processing in five launches (1), the same
  *                  with the exact select forced (2), the unfused pipeline (0);
  *   "rpn_merge"    RPN proposals' level merge by merge rank (1) or the one-
@@ -72,11 +64,10 @@ const char* d2mi_last_error(void);
  *   "conv_stream_nt" streaming 1x1's output stores non-temporal (2);
  *   "conv_nt"      tiled conv final stores non-temporal (0);
  *   "conv_tail_mink" fewest k-steps whose tail tiles are split along K (8);
- *   "conv_ws_mintiles" fewest 256x128 tiles that go to the WS conv (0);
  *   "sgd_rev"      SGD update over its chunks in reverse order (0);
  *   "retina_rank"  RetinaNet merge rank inside the NMS workgroup (0);
- *   "solo_mfma"    SOLOv2 Matrix-NMS intersections on int8 MFMA: 2 (default)
- *                  = bits expanded by an LDS table, 1 = by arithmetic; 0 = the
+ *   "solo_mfma"    SOLOv2 Matrix-NMS intersections on int8 MFMA, bits expanded
+ *                  by an LDS table (2, default; any non-zero value); 0 = the
  *                  AND + popcount tiles;
  *   "retina_var"   RetinaNet fused-path variants (bits; default 12018, 0 = the
  *                  r5 form): 16 = the wave slots compacted by many workgroups
@@ -92,22 +83,18 @@ const char* d2mi_last_error(void);
  *                  rounds capped and looped, 2 = a small level's floor
  *                  samples spread over the level, 4 = floor and finish
  *                  launched twice (measurement only);
- *   "conv_occ"     resident workgroups per CU of the 128x128 conv kernel: 3
- *                  (default), 2 = two;
  *   "conv_split_slots" split-K workgroup target of the convs (0 = the plan's
  *                  own: two per CU, one for the WS conv);
  *   "conv_tail"    tail tiles of a mostly empty last round split along K (1);
  *                  0 = off;
- *   "wgrad_occ"    the 128x128 split weight gradient at three workgroups per
- *                  CU from "wgrad_occ3_min_p" pixels (65536) up: 3 (default),
- *                  2 = two everywhere;
+ *   "wgrad_occ3_min_p" the 128x128 split weight gradient runs three workgroups
+ *                  per CU from this many pixels up (65536);
  *   "wgrad_slots"  pixel-split workgroup target of the weight gradient (0 =
  *                  the plan's own: 256 / 512 / 768 by kernel);
  *   "wgrad_minch"  fewest 32-pixel chunks per split (16; <= 0 = the default);
  *   "wgrad_maxsplit" most pixel splits (128; <= 0 = the default);
  *   "wgrad_prio"   wave priority 1 while issuing MFMAs in the weight gradient
  *                  (1 on);
- *   "roi_bwd_ppw"  ROIAlign backward pixel pass: 8 = eight pixels per wave (0);
  *   "topk_floor"   sampled-floor first pass of the segmented top-k (1); 0 =
  *                  radix passes only. */
 int d2mi_set_tuning(const char* key, int value);

@@ -120,15 +120,16 @@ def test_parser_refuses_a_type_it_does_not_know():
 
 
 TUNING_DEFAULTS = {
-    "conv_ws": 2, "roi_fwd": -1, "wgrad_ws": 1, "conv_epi": 1, "wgrad_ws1": 6, "wgrad_xcd": 1,
-    "conv_xcd": 1, "wgrad_inc": 1, "conv_ws_mink": 16, "roi_pix_grid": 8192, "conv_stream": 8192,
-    "roi_bwd_rec": 1, "retina_fused": 1, "rpn_merge": 1, "nms_scan": 1, "roi_heavy": 16,
-    "rpn_compact": 1, "conv_stream_nt": 2, "conv_nt": 0, "conv_tail_mink": 8,
-    "conv_ws_mintiles": 0, "sgd_rev": 0, "retina_rank": 0, "solo_mfma": 2, "retina_var": 12018,
-    "conv_occ": 3, "conv_split_slots": 0, "conv_tail": 1, "wgrad_occ": 3, "wgrad_occ3_min_p": 65536,
-    "wgrad_slots": 0, "wgrad_minch": 16, "wgrad_maxsplit": 128, "wgrad_prio": 1, "roi_bwd_ppw": 0,
-    "topk_floor": 1,
+    "conv_epi": 1, "wgrad_ws1": 6, "wgrad_xcd": 1, "conv_xcd": 1, "conv_ws_mink": 16,
+    "roi_pix_grid": 8192, "conv_stream": 8192, "retina_fused": 1, "rpn_merge": 1, "nms_scan": 1,
+    "roi_heavy": 16, "rpn_compact": 1, "conv_stream_nt": 2, "conv_nt": 0, "conv_tail_mink": 8,
+    "sgd_rev": 0, "retina_rank": 0, "solo_mfma": 2, "retina_var": 12018, "conv_split_slots": 0,
+    "conv_tail": 1, "wgrad_occ3_min_p": 65536, "wgrad_slots": 0, "wgrad_minch": 16,
+    "wgrad_maxsplit": 128, "wgrad_prio": 1, "topk_floor": 1,
 }
+# knobs fixed at their defaults and removed: unknown keys now
+RETIRED_KNOBS = ("conv_ws", "roi_fwd", "wgrad_ws", "wgrad_inc", "roi_bwd_rec", "conv_ws_mintiles",
+                 "conv_occ", "wgrad_occ", "roi_bwd_ppw")
 
 _TUNING_CHILD = """
 import json, sys
@@ -141,6 +142,15 @@ try:
     out["<unknown set>"] = "accepted"
 except _C.D2MIError as e:
     out["<unknown set>"] = str(e)
+retired = {}
+for k in json.loads(sys.argv[2]):
+    try:
+        ops.set_tuning(k, 1)
+        err = "accepted"
+    except _C.D2MIError as e:
+        err = str(e)
+    retired[k] = [_C.lib().d2mi_get_tuning(k.encode()), err]
+out["<retired>"] = retired
 print(json.dumps(out))
 """
 
@@ -152,22 +162,29 @@ def _tuning_in_child(extra_env):
     import sys
     env = {k: v for k, v in os.environ.items() if not k.startswith("D2MI_")}
     env.update(extra_env, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, "-c", _TUNING_CHILD, json.dumps(list(TUNING_DEFAULTS))],
+    r = subprocess.run([sys.executable, "-c", _TUNING_CHILD, json.dumps(list(TUNING_DEFAULTS)),
+                        json.dumps(list(RETIRED_KNOBS))],
                        env=env, capture_output=True, text=True, cwd=ROOT)
     assert r.returncode == 0, r.stderr
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
 def test_tuning_defaults_and_environment_without_gpu():
-    """The 36 knobs' defaults, their D2MI_<KEY> environment variables, and unknown keys."""
+    """The 27 knobs' defaults, their D2MI_<KEY> environment variables, unknown keys, and the
+    retired knobs among them."""
     from detectron2_tensorflow_amd import _build
     _build.build()
     got = _tuning_in_child({})
     assert got.pop("<unknown get>") == -2 ** 31
     assert "unknown tuning key" in got.pop("<unknown set>")
-    assert got == TUNING_DEFAULTS and len(got) == 36
+    retired = got.pop("<retired>")
+    assert sorted(retired) == sorted(RETIRED_KNOBS)
+    for k, (value, err) in retired.items():
+        assert value == -2 ** 31 and "unknown tuning key" in err, k
+    assert got == TUNING_DEFAULTS and len(got) == 27
     # (D2MI_CONV_TAIL, D2MI_WGRAD_MAXSPLIT: read by bare getenv before they joined the table)
     got = _tuning_in_child({"D2MI_CONV_NT": "1", "D2MI_RETINA_VAR": "0", "D2MI_CONV_TAIL": "0",
                             "D2MI_WGRAD_MAXSPLIT": "4"})
     assert got.pop("<unknown get>") == -2 ** 31 and "unknown tuning key" in got.pop("<unknown set>")
+    got.pop("<retired>")
     assert got == dict(TUNING_DEFAULTS, conv_nt=1, retina_var=0, conv_tail=0, wgrad_maxsplit=4)

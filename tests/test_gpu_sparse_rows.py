@@ -12,7 +12,7 @@ import torch
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CATS = {"num_thing_classes": 80, "num_stuff_classes": 53, "stuff_ignore_value": 0}
-WS_KERNELS = ("ws", "ws_inc", "ws2")
+WS_KERNELS = ("ws", "ws_inc")
 
 
 class _Counter:

@@ -32,11 +32,6 @@ def _rpn_acc(on):
     _RPNHead1x1Fn.ACC_LEVELS = on
 
 
-def _conv_ws(on):
-    from detectron2_tensorflow_amd.layers import ops
-    ops.set_tuning("conv_ws", 2 if on else 0)
-
-
 def _wgrad_ws1(on):
     from detectron2_tensorflow_amd.layers import ops
     ops.set_tuning("wgrad_ws1", 6 if on else 0)
@@ -93,7 +88,7 @@ def _skinny_levels(on):
 
 
 SWITCHES = {"skinny_levels": _skinny_levels, "mask_prep_early": _mask_prep_early, "gc_off": _gc_off, "defer_pixels": _defer_pixels, "rpn_concat": _rpn_concat, "rpn_conv_acc": _rpn_conv_acc, "fpn_join": _fpn_join, "pack_group": _pack_group, "rpn_acc": _rpn_acc,
-            "conv_ws": _conv_ws, "conv_epi": _conv_epi,
+            "conv_epi": _conv_epi,
             "wgrad_ws1": _wgrad_ws1, "stem_mfma": _stem_mfma, "fused_sample": _fused_sample}
 
 

@@ -143,26 +143,8 @@ def main():
     cb = uniq.numel() * C * 4
     cp_src = src[:uniq.numel()].contiguous()
     cp_out = torch.empty_like(cp_src)
-    def roi_tv(v):
-        def fn():
-            old = ops.get_tuning("roi_fwd")
-            ops.set_tuning("roi_fwd", v)
-            try:
-                run_roi()
-            finally:
-                ops.set_tuning("roi_fwd", old)
-        return fn
-
     arms = {
         "roi_align": run_roi,
-        # r6: one wave iteration per wave (bit 16), U = 4 / 2 / 8 bins in flight
-        "roi_align_1it_u4": roi_tv(2 | 4 | 8 | 16),
-        "roi_align_1it_u2": roi_tv(1 | 2 | 4 | 8 | 16),
-        "roi_align_1it_u8": roi_tv(2 | 4 | 8 | 16 | 32),
-        # r6: corner rows loaded non-temporally (bit 64)
-        "roi_align_ntl_u2": roi_tv(1 | 2 | 4 | 8 | 64),
-        "roi_align_ntl_u4": roi_tv(2 | 4 | 8 | 64),
-        "roi_align_ntl_1it_u4": roi_tv(2 | 4 | 8 | 16 | 64),
         # r6: the forward's 4-corner pattern in the guide's shape (scalar
         # corner indices, persistent 16 waves per CU), default / nt loads
         "gather4_s_u2": lambda: lib.gc_gather4_s(src.data_ptr(), idx.data_ptr(), nb, out4.data_ptr(),
@@ -202,16 +184,6 @@ def main():
             tot += e0.elapsed_time(e1)
         return tot / a.iters * 1e3
 
-    for v in (2 | 4 | 8 | 16, 1 | 2 | 4 | 8 | 16, 2 | 4 | 8 | 16 | 32, 1 | 2 | 4 | 8 | 64,
-              2 | 4 | 8 | 64, 2 | 4 | 8 | 16 | 64):
-        old = ops.get_tuning("roi_fwd")
-        ops.set_tuning("roi_fwd", v)
-        try:
-            yv = run_roi()
-        finally:
-            ops.set_tuning("roi_fwd", old)
-        print(f"roi_fwd variant {v}: output equal to the default's: {bool(torch.equal(yv, y))}",
-              flush=True)
     copy_validation(lib, dev, st)
     guide_gather(lib, dev, st, uniq, src, C, flush, a.iters)
     t = {k: [] for k in arms}

@@ -4,7 +4,7 @@ over the training step's conv shapes: every arm's output must be
 bit-identical to arm 0's, and each arm is timed in interleaved rounds (the
 median per shape is printed, then the total).
 
-    python tools/ws_ab.py [--key ws] [--arms 0,2,3] [--set all] [--iters 20] [--rounds 3]
+    python tools/ws_ab.py [--key conv_ws_mink] [--arms 16,1000000] [--set all] [--iters 20] [--rounds 3]
 """
 import argparse
 import os
@@ -21,8 +21,8 @@ from detectron2_tensorflow_amd.layers import ops  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--key", default="conv_ws")
-    ap.add_argument("--arms", default="0,2,3")
+    ap.add_argument("--key", default="conv_ws_mink")
+    ap.add_argument("--arms", default="16,1000000")
     ap.add_argument("--set", default="all")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
