@@ -55,6 +55,12 @@ def _tree():
             "POOLER_SAMPLING_RATIO": 0, "POOLER_TYPE": "ROIAlignV2", "NUM_FC": 0, "FC_DIM": 1024,
             "NUM_CONV": 0, "CONV_DIM": 256, "NORM": "", "CLS_AGNOSTIC_BBOX_REG": False,
         },
+        # (the number of cascade stages is the length of these two)
+        "ROI_BOX_CASCADE_HEAD": {
+            "BBOX_REG_WEIGHTS": ((10.0, 10.0, 5.0, 5.0), (20.0, 20.0, 10.0, 10.0),
+                                 (30.0, 30.0, 15.0, 15.0)),
+            "IOUS": (0.5, 0.6, 0.7),
+        },
         "ROI_MASK_HEAD": {
             "NAME": "MaskRCNNConvUpsampleHead", "POOLER_RESOLUTION": 14,
             "POOLER_SAMPLING_RATIO": 0, "NUM_CONV": 0, "CONV_DIM": 256, "NORM": "",

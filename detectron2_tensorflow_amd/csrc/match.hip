@@ -11,11 +11,11 @@
 //    background, then crowd (-1 where background and max crowd IoU > 1e-3)
 //    and difficult (-1 where background and max difficult IoU > thr[1]).
 //
-// IoU float sequence: ih = min(y2a,y2b) - max(y1a,y1b) clamped at 0, iw the
-// same, inter = ih * iw, union = (area_a + area_b) - inter, inter / union
-// (0 when union == 0): the tensor code's order, so labels are identical.
+// IoU float sequence: iou_of (iou.h), the tensor code's order, so labels are
+// identical.
 #include "common.h"
 #include "internal.h"
+#include "iou.h"
 
 namespace d2mi {
 namespace {
@@ -26,16 +26,6 @@ constexpr int kMaxGt = 256;
 // fewer, fuller workgroups (r6: 16 per thread, 4,096 boxes per workgroup;
 // 4 before: 263 atomics per GT per image at 1333x800)
 constexpr int kBestPer = 16;
-
-__device__ __forceinline__ float iou_of(const float4 a, const float4 b) {
-  const float ih = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.f);
-  const float iw = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.f);
-  const float inter = ih * iw;
-  const float area_a = (a.z - a.x) * (a.w - a.y);
-  const float area_b = (b.z - b.x) * (b.w - b.y);
-  const float uni = area_a + area_b - inter;
-  return uni == 0.f ? 0.f : inter / uni;
-}
 
 __device__ __forceinline__ unsigned ord(float f) {
   const unsigned u = __float_as_uint(f);

@@ -387,6 +387,77 @@ __global__ __launch_bounds__(256) void frcnn_score_kernel(
   if (lane == 0) atomic_max_ordered(&maxc[n], bmax);
 }
 
+// frcnn_score_kernel with the scores averaged over the stages of a cascade
+// (cascade_rcnn.py:123-129): each stage's softmax in the order above, summed
+// left to right ((p0 + p1) + p2) + p3 and multiplied by the f32 value of
+// 1.0 / num_stages (tf.add_n(...) * (1.0 / n)); deltas / dc are the last
+// stage's.  One stage: p0 * 1.0f, the single-stage kernel's value.
+constexpr int kMaxStages = 4;
+struct StageLogits {
+  const float* p[kMaxStages];
+  int n;
+  float inv_n;
+};
+
+__global__ __launch_bounds__(256) void frcnn_score_stages_kernel(
+    StageLogits sl, const float4* __restrict__ deltas, const float4* __restrict__ props,
+    const int32_t* __restrict__ roi_img, const int32_t* __restrict__ roi_slot, int R, int N, int P,
+    int K, int agnostic, const int32_t* __restrict__ image_hw, DeltaCfg dc, float thresh, int cap,
+    uint32_t* __restrict__ maxc, int32_t* __restrict__ cnt, uint64_t* __restrict__ keys,
+    float4* __restrict__ cbox, float* __restrict__ cscore, int32_t* err) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (r >= R) return;
+  const int n = roi_img[r], slot = roi_slot[r];
+  if (n < 0 || n >= N || slot < 0 || slot >= P) return;
+  const float* lg[kMaxStages];
+  float mx[kMaxStages], inv[kMaxStages];
+#pragma unroll
+  for (int s = 0; s < kMaxStages; ++s) {
+    lg[s] = nullptr;
+    mx[s] = 0.f;
+    inv[s] = 0.f;
+    if (s < sl.n) {
+      lg[s] = sl.p[s] + (size_t)r * (K + 1);
+      float m = -INFINITY;
+      for (int c = lane; c <= K; c += 64) m = fmaxf(m, lg[s][c]);
+      m = wave_max(m);
+      float sum = 0.f;
+      for (int c = lane; c <= K; c += 64) sum += expf(lg[s][c] - m);
+      sum = wave_sum(sum);
+      mx[s] = m;
+      inv[s] = 1.f / sum;  // TF softmax: exp(x - max) * (1 / sum)
+    }
+  }
+  const float hmax = (float)image_hw[2 * n], wmax = (float)image_hw[2 * n + 1];
+  const float4 pb = props[r];
+  float bmax = 0.f;
+  for (int c = lane; c < K; c += 64) {
+    float p = expf(lg[0][c] - mx[0]) * inv[0];
+#pragma unroll
+    for (int s = 1; s < kMaxStages; ++s)
+      if (s < sl.n) p = p + expf(lg[s][c] - mx[s]) * inv[s];
+    p = p * sl.inv_n;
+    const float4 d = deltas[(size_t)r * (agnostic ? 1 : K) + (agnostic ? 0 : c)];
+    float4 b = apply_delta(pb, d, dc.wy, dc.wx, dc.wh, dc.ww, dc.clamp);
+    b = clip_box(b, hmax, wmax);
+    bmax = fmaxf(bmax, fmaxf(fmaxf(b.x, b.y), fmaxf(b.z, b.w)));
+    if (p > thresh) {
+      const int pos = atomicAdd(&cnt[n], 1);
+      if (pos < cap) {
+        const size_t o = (size_t)n * cap + pos;
+        keys[o] = desc_key(p, (uint32_t)(c * P + slot));  // class-major tf.where order
+        cbox[o] = b;
+        cscore[o] = p;
+      } else {
+        atomicOr(err, kErrNmsCapacity);
+      }
+    }
+  }
+  bmax = wave_max(bmax);
+  if (lane == 0) atomic_max_ordered(&maxc[n], bmax);
+}
+
 __global__ void clamp_lens_kernel(int32_t* cnt, int N, int cap) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n < N) cnt[n] = min(cnt[n], cap);
@@ -702,8 +773,12 @@ extern "C" int d2mi_rpn_proposals_ex(const float* const* logits, const float* co
                                      void* stream) {
   hipStream_t st = as_stream(stream);
   D2MI_REQUIRE(N >= 1 && pre_nms_topk >= 1 && post_nms_topk >= 1, "bad RPN sizes");
-  D2MI_REQUIRE(L * post_nms_topk <= kLdsSortCap, "L*post_nms_topk=%d exceeds %d", L * post_nms_topk,
-               kLdsSortCap);
+  // the per-image merge holds L * post entries in LDS: 64-bit keys in the
+  // bitonic sort, 32-bit score words next to the merge rank's few static
+  // words in 64 KiB (the cascade configs' POST_NMS_TOPK_TRAIN = 2000 on 5 levels)
+  const int merge_cap = tuning(kTuneRpnMerge) != 0 ? (64 * 1024 - 256) / 4 : kLdsSortCap;
+  D2MI_REQUIRE((long long)L * post_nms_topk <= merge_cap, "L*post_nms_topk=%lld exceeds %d",
+               (long long)L * post_nms_topk, merge_cap);
   Levels lv = {};
   int rc = make_levels(lv, logits, deltas, level_hw, strides, cell_anchors, L, A);
   if (rc) return rc;
@@ -823,15 +898,15 @@ extern "C" size_t d2mi_fast_rcnn_workspace_size(int N, int P, int K, float score
                                max_det);
 }
 
-extern "C" int d2mi_fast_rcnn_inference(const float* logits, const float* deltas,
-                                        const float* proposals, const int32_t* roi_img,
-                                        const int32_t* roi_slot, int R, int N, int P, int K,
-                                        int cls_agnostic, const int32_t* image_hw,
-                                        const float* weights4_host, float scale_clamp,
-                                        float score_thresh, float nms_thresh, int max_det,
-                                        float* out_boxes, float* out_scores, int64_t* out_classes,
-                                        uint8_t* out_valid, int32_t* out_roi, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
+// The pipeline of both entry points.  stages null: d2mi_fast_rcnn_inference
+// (frcnn_score_kernel on logits); else the stage-averaged score kernel.
+static int frcnn_run(const float* logits, const StageLogits* stages, const float* deltas,
+                     const float* proposals, const int32_t* roi_img, const int32_t* roi_slot,
+                     int R, int N, int P, int K, int cls_agnostic, const int32_t* image_hw,
+                     const float* weights4_host, float scale_clamp, float score_thresh,
+                     float nms_thresh, int max_det, float* out_boxes, float* out_scores,
+                     int64_t* out_classes, uint8_t* out_valid, int32_t* out_roi, void* workspace,
+                     size_t workspace_bytes, void* stream) {
   hipStream_t st = as_stream(stream);
   D2MI_REQUIRE(N >= 1 && P >= 1 && K >= 1 && R >= 0 && max_det >= 1 && max_det <= 1000,
                "bad fast_rcnn_inference sizes");
@@ -856,11 +931,18 @@ extern "C" int d2mi_fast_rcnn_inference(const float* logits, const float* deltas
     hipLaunchKernelGGL(slot_map_kernel, dim3((R + 255) / 256), dim3(256), 0, st, roi_img, roi_slot,
                        R, P, N, o.slot2roi, err);
     D2MI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(frcnn_score_kernel, dim3((R + 3) / 4), dim3(256), 0, st, logits,
-                       reinterpret_cast<const float4*>(deltas),
-                       reinterpret_cast<const float4*>(proposals), roi_img, roi_slot, R, N, P, K,
-                       agnostic_box, image_hw, make_dc(weights4_host, scale_clamp), score_thresh,
-                       cap, o.maxc, o.cnt, o.keys, o.cbox, o.cscore, err);
+    if (stages == nullptr)
+      hipLaunchKernelGGL(frcnn_score_kernel, dim3((R + 3) / 4), dim3(256), 0, st, logits,
+                         reinterpret_cast<const float4*>(deltas),
+                         reinterpret_cast<const float4*>(proposals), roi_img, roi_slot, R, N, P, K,
+                         agnostic_box, image_hw, make_dc(weights4_host, scale_clamp), score_thresh,
+                         cap, o.maxc, o.cnt, o.keys, o.cbox, o.cscore, err);
+    else
+      hipLaunchKernelGGL(frcnn_score_stages_kernel, dim3((R + 3) / 4), dim3(256), 0, st, *stages,
+                         reinterpret_cast<const float4*>(deltas),
+                         reinterpret_cast<const float4*>(proposals), roi_img, roi_slot, R, N, P, K,
+                         agnostic_box, image_hw, make_dc(weights4_host, scale_clamp), score_thresh,
+                         cap, o.maxc, o.cnt, o.keys, o.cbox, o.cscore, err);
     D2MI_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(clamp_lens_kernel, dim3((N + 255) / 256), dim3(256), 0, st, o.cnt, N, cap);
@@ -883,6 +965,46 @@ extern "C" int d2mi_fast_rcnn_inference(const float* logits, const float* deltas
                      out_roi);
   D2MI_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int d2mi_fast_rcnn_inference(const float* logits, const float* deltas,
+                                        const float* proposals, const int32_t* roi_img,
+                                        const int32_t* roi_slot, int R, int N, int P, int K,
+                                        int cls_agnostic, const int32_t* image_hw,
+                                        const float* weights4_host, float scale_clamp,
+                                        float score_thresh, float nms_thresh, int max_det,
+                                        float* out_boxes, float* out_scores, int64_t* out_classes,
+                                        uint8_t* out_valid, int32_t* out_roi, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  return frcnn_run(logits, nullptr, deltas, proposals, roi_img, roi_slot, R, N, P, K,
+                   cls_agnostic, image_hw, weights4_host, scale_clamp, score_thresh, nms_thresh,
+                   max_det, out_boxes, out_scores, out_classes, out_valid, out_roi, workspace,
+                   workspace_bytes, stream);
+}
+
+extern "C" int d2mi_fast_rcnn_inference_stages(
+    const float* logits0, const float* logits1, const float* logits2, const float* logits3,
+    int num_stages, const float* deltas, const float* proposals, const int32_t* roi_img,
+    const int32_t* roi_slot, int R, int N, int P, int K, int cls_agnostic,
+    const int32_t* image_hw, const float* weights4_host, float scale_clamp, float score_thresh,
+    float nms_thresh, int max_det, float* out_boxes, float* out_scores, int64_t* out_classes,
+    uint8_t* out_valid, int32_t* out_roi, void* workspace, size_t workspace_bytes, void* stream) {
+  D2MI_REQUIRE(num_stages >= 1 && num_stages <= kMaxStages,
+               "fast_rcnn_inference_stages: num_stages must be 1..%d (got %d)", kMaxStages,
+               num_stages);
+  StageLogits sl;
+  const float* lg[kMaxStages] = {logits0, logits1, logits2, logits3};
+  for (int s = 0; s < kMaxStages; ++s) {
+    D2MI_REQUIRE(s >= num_stages || lg[s] != nullptr || R == 0,
+                 "fast_rcnn_inference_stages: logits%d is null", s);
+    sl.p[s] = s < num_stages ? lg[s] : nullptr;
+  }
+  sl.n = num_stages;
+  sl.inv_n = (float)(1.0 / (double)num_stages);
+  return frcnn_run(nullptr, &sl, deltas, proposals, roi_img, roi_slot, R, N, P, K, cls_agnostic,
+                   image_hw, weights4_host, scale_clamp, score_thresh, nms_thresh, max_det,
+                   out_boxes, out_scores, out_classes, out_valid, out_roi, workspace,
+                   workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------ RetinaNet

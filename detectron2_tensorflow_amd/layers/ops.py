@@ -1198,6 +1198,130 @@ def match_boxes_masks(gt_boxes, valid, boxes, thresholds, labels_of, allow_low_q
     return matches, labels
 
 
+def _cascade_refine_tensor(deltas, boxes, valid, image_hw, weights, scale_clamp, gt, iou_thr,
+                           num_classes):
+    """cascade_refine as tensor ops (any device): the float sequences of
+    apply_delta / clip_box (csrc/common.h) and the matcher's tensor code."""
+    N, S = valid.shape
+    b = boxes.reshape(N * S, 4)
+    d = deltas.reshape(N * S, 4)
+    wy, wx, wh, ww = (float(w) for w in weights)
+    h, w = b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]
+    cy, cx = b[:, 0] + 0.5 * h, b[:, 1] + 0.5 * w
+    dh = (d[:, 2] / wh).clamp(max=scale_clamp)
+    dw = (d[:, 3] / ww).clamp(max=scale_clamp)
+    pcy, pcx = (d[:, 0] / wy) * h + cy, (d[:, 1] / wx) * w + cx
+    ph, pw = torch.exp(dh) * h, torch.exp(dw) * w
+    dec = torch.stack([pcy - 0.5 * ph, pcx - 0.5 * pw, pcy + 0.5 * ph, pcx + 0.5 * pw], dim=1)
+    hw = image_hw.to(torch.float32)
+    win = torch.stack([hw[:, 0], hw[:, 1], hw[:, 0], hw[:, 1]], dim=1)[:, None, :]  # [N, 1, 4]
+    out = torch.minimum(dec.reshape(N, S, 4), win).clamp(min=0.0)
+    if gt is None:
+        return {"boxes": out, "is_valid": valid}
+    from ..modeling.matcher import Matcher, match_boxes as match_tensor
+    gt_boxes, gt_valid, gt_classes, crowd, difficult = gt
+    area = (out[..., 2] - out[..., 0]) * (out[..., 3] - out[..., 1])
+    ok = valid & (area > 0)
+    matches, labels = match_tensor(Matcher([float(iou_thr)], [0, 1], False), gt_boxes, gt_valid,
+                                   out, crowd=crowd, difficult=difficult)
+    gcls = torch.gather(gt_classes.long(), 1, matches)
+    cls = torch.where(labels == 1, gcls, torch.where(labels == 0, int(num_classes), -1))
+    cls = torch.where(ok, cls, -1)
+    return {"boxes": out, "is_valid": ok, "gt_classes": cls, "gt_index": matches,
+            "gt_boxes": torch.gather(gt_boxes, 1, matches[..., None].expand(-1, -1, 4)),
+            "loss_valid": ok & (cls >= 0)}
+
+
+def cascade_refine(deltas, boxes, valid, image_hw, weights, scale_clamp=_DEFAULT_SCALE_CLAMP,
+                   gt_boxes=None, gt_valid=None, gt_classes=None, gt_crowd=None,
+                   gt_difficult=None, iou_thr=None, num_classes=None):
+    """The stage hand-over of a cascade (cascade_rcnn.py:141-215, :244-273;
+    d2mi_cascade_refine, one launch): the previous stage's class-agnostic
+    deltas [N*S, 4] decoded on its boxes [N, S, 4] with its weights, clipped
+    to the image.  Inference (gt_boxes None): {boxes, is_valid = valid}.
+    Training: is_valid = valid & (area > 0), and the boxes re-matched against
+    the ground truth at iou_thr (labels [0, 1], no low-quality matches,
+    Matcher's crowd / difficult rules): gt_classes (class / num_classes / -1
+    for ignored or invalid rows), gt_index (into the [G] list), gt_boxes,
+    loss_valid = is_valid & (gt_classes >= 0).  Nothing is differentiable."""
+    training = gt_boxes is not None
+    if training and (gt_valid is None or gt_classes is None or iou_thr is None
+                     or num_classes is None):
+        raise ValueError("cascade_refine: training mode needs gt_valid, gt_classes, iou_thr and "
+                         "num_classes")
+    deltas, boxes = deltas.detach(), boxes.detach()
+    N, S = valid.shape
+    if tuple(boxes.shape) != (N, S, 4) or deltas.numel() != N * S * 4:
+        raise ValueError("cascade_refine: boxes [N, S, 4], class-agnostic deltas [N*S, 4], "
+                         "valid [N, S]")
+    valid = valid.to(torch.bool)
+    if not boxes.is_cuda:
+        gt = ((gt_boxes.to(torch.float32), gt_valid.to(torch.bool), gt_classes,
+               gt_crowd.to(torch.bool) if gt_crowd is not None else None,
+               gt_difficult.to(torch.bool) if gt_difficult is not None else None)
+              if training else None)
+        return _cascade_refine_tensor(deltas.to(torch.float32), boxes.to(torch.float32), valid,
+                                      image_hw, weights, scale_clamp, gt, iou_thr, num_classes)
+    deltas, boxes, image_hw = _f32c(deltas), _f32c(boxes), _i32c(image_hw)
+    v = _mask_u8(valid)
+    _C.require_device(deltas, boxes, v, image_hw)
+    dev = boxes.device
+    ob = torch.empty((N, S, 4), dtype=torch.float32, device=dev)
+    ov = torch.empty((N, S), dtype=torch.bool, device=dev)
+    w4 = _C.host_array(_C.c_float, [float(w) for w in weights])
+    nul = _C.c_void_p(None)
+    if not training:
+        rc = _C.lib().d2mi_cascade_refine(_C.ptr(deltas), _C.ptr(boxes), _C.ptr(v),
+                                          _C.ptr(image_hw), N, S, w4, float(scale_clamp), 0, nul,
+                                          nul, nul, nul, nul, 0, 0, 0.0, 0, _C.ptr(ob), _C.ptr(ov),
+                                          nul, nul, nul, nul, _C.stream_of(dev))
+        _C.check(rc, "d2mi_cascade_refine")
+        return {"boxes": ob, "is_valid": ov}
+    gt_boxes = _f32c(gt_boxes)
+    m, c, d = _mask_u8(gt_valid), _mask_u8(gt_crowd), _mask_u8(gt_difficult)
+    if gt_classes.dtype not in (torch.int32, torch.int64):
+        gt_classes = gt_classes.to(torch.int64)
+    gt_classes = gt_classes.contiguous()
+    _C.require_device(gt_boxes, m, gt_classes, *[t for t in (c, d) if t is not None])
+    G = m.shape[1]
+    for t in (gt_classes, c, d):
+        if t is not None and tuple(t.shape) != (N, G):
+            raise ValueError("cascade_refine: gt_classes / crowd / difficult must be [N, G]")
+    if tuple(gt_boxes.shape) != (N, G, 4):
+        raise ValueError("cascade_refine: gt_boxes must be [N, G, 4]")
+    ocls = torch.empty((N, S), dtype=torch.int64, device=dev)
+    oidx = torch.empty((N, S), dtype=torch.int64, device=dev)
+    ogtb = torch.empty((N, S, 4), dtype=torch.float32, device=dev)
+    olv = torch.empty((N, S), dtype=torch.bool, device=dev)
+    rc = _C.lib().d2mi_cascade_refine(
+        _C.ptr(deltas), _C.ptr(boxes), _C.ptr(v), _C.ptr(image_hw), N, S, w4, float(scale_clamp),
+        1, _C.ptr(gt_boxes), _C.ptr(m), _C.ptr(c) if c is not None else nul,
+        _C.ptr(d) if d is not None else nul, _C.ptr(gt_classes),
+        int(gt_classes.dtype is torch.int64), G, float(iou_thr), int(num_classes), _C.ptr(ob),
+        _C.ptr(ov), _C.ptr(ocls), _C.ptr(oidx), _C.ptr(ogtb), _C.ptr(olv), _C.stream_of(dev))
+    _C.check(rc, "d2mi_cascade_refine")
+    return {"boxes": ob, "is_valid": ov, "gt_classes": ocls, "gt_index": oidx, "gt_boxes": ogtb,
+            "loss_valid": olv}
+
+
+class _ScaleGradFn(torch.autograd.Function):
+    """Identity forward, gradient * scale backward (cascade_rcnn.py:35-39)."""
+
+    @staticmethod
+    def forward(ctx, x, scale):
+        ctx.scale = scale
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.scale, None
+
+
+def scale_gradient(x, scale):
+    """x unchanged; the gradient reaching x is multiplied by scale."""
+    return _ScaleGradFn.apply(x, float(scale))
+
+
 class _RPNLossFn(torch.autograd.Function):
     """(loss_cls_sum, loss_loc_sum) * scale of the RPN (d2mi_rpn_loss_fwd /
     d2mi_rpn_loss_bwd_ex); differentiable w.r.t. logits and deltas.  The scale
@@ -2165,6 +2289,46 @@ def fast_rcnn_inference(logits, deltas, proposals, roi_img, roi_slot, num_images
         float(score_thresh), float(nms_thresh), int(topk_per_image), _C.ptr(ob), _C.ptr(os_),
         _C.ptr(oc), _C.ptr(ov), _C.ptr(oroi), _C.ptr(ws), wsb, _C.stream_of(dev))
     _C.check(rc, "d2mi_fast_rcnn_inference")
+    return ob, os_, oc, ov.bool(), oroi
+
+
+def fast_rcnn_inference_stages(stage_logits, deltas, proposals, roi_img, roi_slot, num_images, P,
+                               image_hw, weights, score_thresh, nms_thresh, topk_per_image,
+                               cls_agnostic=False, scale_clamp=_DEFAULT_SCALE_CLAMP,
+                               nms_cls_agnostic=False):
+    """fast_rcnn_inference on the class scores of a cascade averaged over its
+    stages (cascade_rcnn.py:123-139; d2mi_fast_rcnn_inference_stages):
+    stage_logits is the list of 1..4 per-stage logits [R, K+1]; deltas,
+    proposals and weights are the last stage's."""
+    stage_logits = [_f32c(t) for t in stage_logits]
+    if not 1 <= len(stage_logits) <= 4:
+        raise ValueError(f"fast_rcnn_inference_stages: 1..4 stages (got {len(stage_logits)})")
+    if any(t.shape != stage_logits[0].shape for t in stage_logits):
+        raise ValueError("fast_rcnn_inference_stages: every stage's logits must be [R, K+1]")
+    deltas, proposals = _f32c(deltas), _f32c(proposals)
+    roi_img, roi_slot, image_hw = _i32c(roi_img), _i32c(roi_slot), _i32c(image_hw)
+    _C.require_device(*stage_logits, deltas, proposals, roi_img, roi_slot, image_hw)
+    R, K1 = stage_logits[0].shape
+    K = K1 - 1
+    N = int(num_images)
+    dev = deltas.device
+    ob = torch.empty((N, topk_per_image, 4), dtype=torch.float32, device=dev)
+    os_ = torch.empty((N, topk_per_image), dtype=torch.float32, device=dev)
+    oc = torch.empty((N, topk_per_image), dtype=torch.int64, device=dev)
+    ov = torch.empty((N, topk_per_image), dtype=torch.uint8, device=dev)
+    oroi = torch.empty((N, topk_per_image), dtype=torch.int32, device=dev)
+    wsb = _C.lib().d2mi_fast_rcnn_workspace_size(N, int(P), K, float(score_thresh),
+                                                 int(topk_per_image))
+    ws = _C.workspace(wsb, dev)
+    lp = [_C.ptr(t) for t in stage_logits] + [None] * (4 - len(stage_logits))
+    rc = _C.lib().d2mi_fast_rcnn_inference_stages(
+        *lp, len(stage_logits), _C.ptr(deltas), _C.ptr(proposals), _C.ptr(roi_img),
+        _C.ptr(roi_slot), R, N, int(P), K,
+        int(bool(cls_agnostic)) | (int(bool(nms_cls_agnostic)) << 1), _C.ptr(image_hw),
+        _C.host_array(_C.c_float, [float(w) for w in weights]), float(scale_clamp),
+        float(score_thresh), float(nms_thresh), int(topk_per_image), _C.ptr(ob), _C.ptr(os_),
+        _C.ptr(oc), _C.ptr(ov), _C.ptr(oroi), _C.ptr(ws), wsb, _C.stream_of(dev))
+    _C.check(rc, "d2mi_fast_rcnn_inference_stages")
     return ob, os_, oc, ov.bool(), oroi
 
 

@@ -82,7 +82,10 @@ def calibrate_rcnn_scores(model, batch):
         return hook
 
     rh = model.roi_heads
-    h1 = rh.box_predictor.register_forward_hook(grab("box"))
+    # (a cascade's predictors, one per stage: each calibrated on its own input)
+    preds = rh.box_predictor
+    preds = list(preds) if isinstance(preds, (list, tuple, torch.nn.ModuleList)) else [preds]
+    h1 = [p.register_forward_hook(grab(f"box{i}")) for i, p in enumerate(preds)]
     rpn_head = model.proposal_generator.rpn_head
     # the shared conv's output on the last level (the head returns them all)
     h2 = rpn_head.register_forward_hook(lambda m, i, o: stats.__setitem__(
@@ -93,16 +96,18 @@ def calibrate_rcnn_scores(model, batch):
     model.eval()
     model.inference({"image": batch["image"], "image_shape": batch["image_shape"]})
     model.train(was)
-    h1.remove()
+    for h in h1:
+        h.remove()
     h2.remove()
     if h3 is not None:
         h3.remove()
-    cls = rh.box_predictor.cls_score
-    cls.weights.normal_(0.0, 3.0 / math.sqrt(max(stats["box"], 1e-12)))
+    for i, p in enumerate(preds):
+        p.cls_score.weights.normal_(0.0, 3.0 / math.sqrt(max(stats[f"box{i}"], 1e-12)))
     obj = rpn_head.objectness_logits
     obj.weights.normal_(0.0, 1.0 / math.sqrt(max(stats["rpn"], 1e-12)))
     rpn_head.anchor_deltas.weights.normal_(0.0, 0.1 / math.sqrt(max(stats["rpn"], 1e-12)))
-    rh.box_predictor.bbox_pred.weights.normal_(0.0, 0.5 / math.sqrt(max(stats["box"], 1e-12)))
+    for i, p in enumerate(preds):
+        p.bbox_pred.weights.normal_(0.0, 0.5 / math.sqrt(max(stats[f"box{i}"], 1e-12)))
     if "mask" in stats:
         mask_pred.weights.normal_(0.0, 1.0 / math.sqrt(max(stats["mask"], 1e-12)))
 

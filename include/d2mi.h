@@ -342,6 +342,23 @@ int d2mi_fast_rcnn_inference(const float* logits, const float* deltas, const flo
                              float nms_thresh, int max_det, float* out_boxes, float* out_scores,
                              int64_t* out_classes, uint8_t* out_valid, int32_t* out_roi,
                              void* workspace, size_t workspace_bytes, void* stream);
+/* d2mi_fast_rcnn_inference on the scores of a cascade averaged over its
+ * stages (cascade_rcnn.py:123-139): logits0..logits3 [R, K+1], the first
+ * num_stages (1..4) of them used, the others null.  Each stage's softmax in
+ * the single-stage order, summed left to right and multiplied by the f32
+ * value of 1.0 / num_stages; deltas / weights4_host are the last stage's.
+ * Same workspace (d2mi_fast_rcnn_workspace_size); num_stages = 1 gives
+ * d2mi_fast_rcnn_inference's outputs bit for bit. */
+int d2mi_fast_rcnn_inference_stages(const float* logits0, const float* logits1,
+                                    const float* logits2, const float* logits3, int num_stages,
+                                    const float* deltas, const float* proposals,
+                                    const int32_t* roi_img, const int32_t* roi_slot, int R, int N,
+                                    int P, int K, int cls_agnostic, const int32_t* image_hw,
+                                    const float* weights4_host, float scale_clamp,
+                                    float score_thresh, float nms_thresh, int max_det,
+                                    float* out_boxes, float* out_scores, int64_t* out_classes,
+                                    uint8_t* out_valid, int32_t* out_roi, void* workspace,
+                                    size_t workspace_bytes, void* stream);
 
 /* --------------------------------------------------- RetinaNet inference
  * RetinaNetHead.inference (retinanet.py:285-387): per level sigmoid,
@@ -816,6 +833,37 @@ int d2mi_match_boxes_ex(const float* gt_boxes, const uint8_t* valid, const uint8
                         int n_intervals, int allow_low_quality, float crowd_thr,
                         float difficult_thr, long long* matches, long long* labels,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------ Cascade R-CNN stage hand-over
+ * CascadeROIHeads._create_proposals_from_boxes + _match_and_label_boxes
+ * (lib/modeling/roi_heads/cascade_rcnn.py:141-215, :244-273) in one launch,
+ * one thread per proposal.  deltas [N*S, 4] (class-agnostic) of the previous
+ * stage decoded on its boxes [N, S, 4] (yxyx f32, 16-B aligned) with
+ * weights4_host / scale_clamp and clipped to [0, 0, h, w] of image_hw int32
+ * [N, 2] -> out_boxes [N, S, 4]; valid / out_valid uint8 [N, S].
+ * training = 0: out_valid = valid and the other outputs are not touched
+ * (null allowed).  training = 1: out_valid = valid && area(out box) > 0, and
+ * the boxes are matched against gt_boxes [N, G, 4] (1 <= G <= 256; gt_valid /
+ * gt_crowd / gt_difficult uint8 [N, G], crowd / difficult nullable, as in
+ * d2mi_match_boxes_ex; gt_cls [N, G] int64 when gt_cls_64 else int32, as in
+ * d2mi_roi_gt_classes) like d2mi_match_boxes_ex with thresholds [-inf,
+ * iou_thr, +inf], labels [0, 1], no low-quality matches, crowd_thr 1e-3 and
+ * difficult_thr iou_thr: out_gt_index int64 = the match, out_gt_boxes
+ * [N, S, 4] = its box, out_gt_classes int64 = its class (foreground) /
+ * num_classes (background) / -1 (ignored, or !out_valid), out_loss_valid
+ * uint8 = out_valid && class >= 0.  Every element of every output is
+ * written; no workspace.  G = 0 is refused in training mode, unlike in
+ * d2mi_match_boxes_ex: the matched class and box are gathered from row
+ * out_gt_index, which needs a GT row to exist (pad the GT list to G >= 1
+ * with gt_valid 0: every row is then background with match 0). */
+int d2mi_cascade_refine(const float* deltas, const float* boxes, const uint8_t* valid,
+                        const int32_t* image_hw, int N, int S, const float* weights4_host,
+                        float scale_clamp, int training, const float* gt_boxes,
+                        const uint8_t* gt_valid, const uint8_t* gt_crowd,
+                        const uint8_t* gt_difficult, const void* gt_cls, int gt_cls_64, int G,
+                        float iou_thr, int num_classes, float* out_boxes, uint8_t* out_valid,
+                        int64_t* out_gt_classes, int64_t* out_gt_index, float* out_gt_boxes,
+                        uint8_t* out_loss_valid, void* stream);
 
 /* ------------------------------------------------ RPN losses
  * RPNOutputs.losses (rpn_outputs.py:306-401) after matching and sampling:

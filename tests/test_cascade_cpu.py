@@ -1,0 +1,263 @@
+"""Cascade R-CNN without a GPU: the two cascade configs build, the model
+carries the converter's variable names and loads a detectron2-named state
+dict, the tensor formulation of ops.cascade_refine equals the restatement
+built from the oracle (tests/cascade_reference.py) on the rows that decide
+its semantics, the 1 / num_stages gradient scale, and the host-side argument
+checks of the two new C entry points."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import cascade_reference as cref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CATS = {"num_thing_classes": 80, "num_stuff_classes": 53, "stuff_ignore_value": 0}
+CASCADE = "Misc/cascade_mask_rcnn_R_50_FPN_3x.yaml"
+PANOPTIC_CASCADE = "Misc/panoptic_fpn_R_101_dconv_cascade_gn_3x.yaml"
+
+
+def _build(yaml, seed=0):
+    from detectron2_tensorflow_amd.config import finalize, get_cfg
+    from detectron2_tensorflow_amd.modeling import build_model
+    cfg = get_cfg()
+    cfg.merge_from_file(os.path.join(ROOT, "configs", yaml))
+    if cfg.MODEL.META_ARCHITECTURE != "PanopticFPN":  # (panoptic needs image-size masks)
+        cfg.MODEL.SEGMENTATION_OUTPUT.FORMAT = "raw"
+    finalize(cfg, False, 1, CATS)
+    torch.manual_seed(seed)
+    return cfg, build_model(cfg)
+
+
+@pytest.mark.parametrize("yaml", [CASCADE, PANOPTIC_CASCADE])
+def test_cascade_configs_build_with_the_converter_names(yaml):
+    from detectron2_tensorflow_amd.modeling import CascadeROIHeads
+    _, model = _build(yaml)
+    rh = model.roi_heads
+    assert isinstance(rh, CascadeROIHeads) and rh.num_cascade_stages == 3
+    assert len(rh.box_head) == len(rh.box_predictor) == len(rh.box2box_transform) == 3
+    assert [t.weights for t in rh.box2box_transform] == [(10, 10, 5, 5), (20, 20, 10, 10),
+                                                         (30, 30, 15, 15)]
+    assert rh.proposal_matchers[0] is None
+    assert [m.thresholds[1] for m in rh.proposal_matchers[1:]] == [0.6, 0.7]
+    names = {n: tuple(t.shape) for n, t in model.reference_variables(include_scope=False)}
+    for k in (1, 2, 3):
+        assert names[f"roi_heads/box_predictor_stage{k}/box_deltas/weights"] == (1024, 4)
+        assert names[f"roi_heads/box_predictor_stage{k}/class_logits/weights"] == (1024, 81)
+        assert f"roi_heads/box_head_stage{k}/fc1/weights" in names
+    assert not [n for n in names if n.startswith(("roi_heads/box_predictor/",
+                                                  "roi_heads/box_head/"))]
+
+
+def test_cascade_constructor_asserts():
+    from detectron2_tensorflow_amd.config import finalize, get_cfg
+    from detectron2_tensorflow_amd.modeling import build_model
+
+    def cfg_with(edit):
+        cfg = get_cfg()
+        cfg.merge_from_file(os.path.join(ROOT, "configs", CASCADE))
+        edit(cfg)
+        finalize(cfg, False, 1, CATS)
+        return cfg
+
+    def not_agnostic(c):
+        c.MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG = False
+
+    def two_ious(c):
+        c.MODEL.ROI_BOX_CASCADE_HEAD.IOUS = (0.5, 0.6)
+
+    def first_iou(c):
+        c.MODEL.ROI_BOX_CASCADE_HEAD.IOUS = (0.4, 0.6, 0.7)
+
+    for edit in (not_agnostic, two_ious, first_iou):
+        with pytest.raises(AssertionError):
+            build_model(cfg_with(edit))
+
+
+def _export_cascade_d2(model, cfg):
+    """The model's tensors under detectron2's names and layouts: the standard
+    parts through test_checkpoint._export_d2, the cascade heads here
+    (roi_heads.box_head.{k}.fc{i}, roi_heads.box_predictor.{k}.{cls_score,bbox_pred})."""
+    from detectron2_tensorflow_amd.checkpoint.convert_d2 import _box_indices
+    from test_checkpoint import _export_d2
+    res, fc_in = cfg.MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION, cfg.MODEL.NECK.OUT_CHANNELS
+
+    class Rest:
+        @staticmethod
+        def reference_variables(include_scope=False):
+            for n, t in model.reference_variables(include_scope=False):
+                if "_stage" not in n:
+                    yield n, t
+
+    d = _export_d2(Rest, cfg)
+    for name, t in model.reference_variables(include_scope=False):
+        if "_stage" not in name:
+            continue
+        _, scope, layer, leaf = name.split("/")
+        kind, k = scope.split("_stage")
+        src = f"roi_heads.{kind}.{int(k) - 1}." + {"class_logits": "cls_score",
+                                                  "box_deltas": "bbox_pred"}.get(layer, layer)
+        v = t.detach().numpy().copy()
+        if leaf == "bias":
+            d[src + ".bias"] = v[_box_indices(1)] if layer == "box_deltas" else v
+            continue
+        if layer == "fc1":
+            v = v.reshape(res, res, fc_in, -1).transpose(2, 0, 1, 3).reshape(res * res * fc_in, -1)
+        if layer == "box_deltas":
+            v = v[..., _box_indices(1)]
+        d[src + ".weight"] = np.ascontiguousarray(v.T)
+    return d
+
+
+def test_cascade_detectron2_checkpoint_loads_strict():
+    from detectron2_tensorflow_amd.checkpoint import load_detectron2_checkpoint
+    cfg, a = _build(CASCADE, 0)
+    _, b = _build(CASCADE, 1)
+    with torch.no_grad():
+        for _, t in a.reference_variables(include_scope=False):
+            t.copy_(torch.rand_like(t) + 0.5)
+    d = _export_cascade_d2(a, cfg)
+    assert "roi_heads.box_head.2.fc1.weight" in d and "roi_heads.box_predictor.0.bbox_pred.bias" in d
+    missing, unexpected = load_detectron2_checkpoint(b, d, cfg, strict=True)
+    assert not missing and not unexpected
+    for (na, ta), (nb, tb) in zip(a.reference_variables(include_scope=False),
+                                  b.reference_variables(include_scope=False)):
+        assert na == nb
+        torch.testing.assert_close(tb, ta, rtol=0, atol=0, msg=na)
+
+
+def _refine_cpu(thr, training=True, with_masks=True):
+    from detectron2_tensorflow_amd.layers import ops
+    deltas, boxes, valid, image_hw, gt = cref.hand_made_case()
+    w = (10.0, 10.0, 5.0, 5.0)
+    kw = {}
+    if training:
+        kw = dict(gt_boxes=torch.from_numpy(gt["gt_boxes"]), gt_valid=torch.from_numpy(gt["is_valid"]),
+                  gt_classes=torch.from_numpy(gt["gt_classes"]), iou_thr=thr, num_classes=80)
+        if with_masks:
+            kw.update(gt_crowd=torch.from_numpy(gt["gt_is_crowd"]),
+                      gt_difficult=torch.from_numpy(gt["gt_difficult"]))
+    got = ops.cascade_refine(torch.from_numpy(deltas), torch.from_numpy(boxes),
+                             torch.from_numpy(valid), torch.from_numpy(image_hw), w, **kw)
+    got = {k: v.numpy() for k, v in got.items()}
+    want = cref.refine(deltas, boxes, valid, image_hw, w, gt if training else None, thr, 80,
+                       decoded=got["boxes"] if training else None)
+    return got, want
+
+
+@pytest.mark.parametrize("thr", [0.5, 0.6])
+def test_cascade_refine_tensor_path_matches_the_restatement(thr):
+    from test_gpu_ops import assert_boxes_close
+    got, want = _refine_cpu(thr)
+    assert set(got) == set(want) == {"boxes", "is_valid", "gt_classes", "gt_index", "gt_boxes",
+                                    "loss_valid"}
+    assert_boxes_close(got["boxes"], want["boxes"])
+    for k in ("is_valid", "gt_classes", "gt_index", "gt_boxes", "loss_valid"):
+        assert got[k].dtype == want[k].dtype, k
+        np.testing.assert_array_equal(got[k], want[k], err_msg=k)
+    v, c, i, lv = got["is_valid"], got["gt_classes"], got["gt_index"], got["loss_valid"]
+    # row 0: decoded outside the image -> clipped to area 0 -> invalid, class -1
+    assert not v[0, 0] and c[0, 0] == -1 and not lv[0, 0]
+    assert (got["boxes"][0, 0] == [100, 120, 100, 120]).all()
+    # row 1: two identical GT, the first wins
+    assert v[0, 1] and i[0, 1] == 0 and c[0, 1] == 3
+    # row 2: IoU exactly 0.5 -> foreground at 0.5, background at 0.6
+    assert c[0, 2] == (11 if thr == 0.5 else 80) and i[0, 2] == 2 and lv[0, 2]
+    # row 3: background inside a crowd GT -> ignored, but still a valid box
+    assert c[0, 3] == -1 and v[0, 3] and not lv[0, 3]
+    # row 4: an invalid input slot stays invalid
+    assert not v[0, 4] and c[0, 4] == -1 and not lv[0, 4]
+    # image 1: no valid GT -> every valid row background with match 0
+    assert (c[1][v[1]] == 80).all() and (i[1] == 0).all() and v[1].sum() > 50
+    assert (lv == (v & (c >= 0))).all()
+
+
+def test_cascade_refine_tensor_path_inference_and_no_masks():
+    from test_gpu_ops import assert_boxes_close
+    got, want = _refine_cpu(0.5, training=False)
+    assert set(got) == {"boxes", "is_valid"}
+    assert_boxes_close(got["boxes"], want["boxes"])
+    # inference: validity passes through (row 0's empty box stays valid)
+    np.testing.assert_array_equal(got["is_valid"], want["is_valid"])
+    assert got["is_valid"][0, 0] and not got["is_valid"][0, 4]
+    # without the crowd mask, row 3 is plain background
+    got, _ = _refine_cpu(0.5, with_masks=False)
+    assert got["gt_classes"][0, 3] == 80 and got["loss_valid"][0, 3]
+
+
+def test_stage_gradient_scale_is_one_third():
+    """The gradient reaching each stage's pooled features is 1/3 of the
+    gradient without the scale (bit for bit: one f32 multiply)."""
+    from detectron2_tensorflow_amd.layers import ops
+    torch.manual_seed(0)
+    heads = [torch.nn.Sequential(torch.nn.Linear(12, 8), torch.nn.ReLU(), torch.nn.Linear(8, 5))
+             for _ in range(3)]
+    pooled = [torch.randn(6, 12, requires_grad=True) for _ in range(3)]
+
+    def grads(scaled):
+        loss = 0
+        for h, x in zip(heads, pooled):
+            y = ops.scale_gradient(x, 1.0 / 3) if scaled else x
+            if scaled:
+                assert torch.equal(y, x)
+            loss = loss + torch.nn.functional.cross_entropy(h(y), torch.arange(6) % 5)
+        return torch.autograd.grad(loss, pooled)
+
+    for g_scaled, g_plain in zip(grads(True), grads(False)):
+        assert g_plain.abs().max() > 0
+        assert torch.equal(g_scaled, g_plain * (1.0 / 3))
+
+
+def test_new_entry_points_refuse_bad_arguments_without_gpu():
+    """Argument validation happens on the host before any launch."""
+    from detectron2_tensorflow_amd import _C
+    lib = _C.load()
+    w = _C.host_array(_C.c_float, [10.0, 10.0, 5.0, 5.0])
+    a = ctypes.c_void_p(4096)  # aligned, never dereferenced: refused first
+
+    def refine(G=5, boxes=a):
+        return lib.d2mi_cascade_refine(a, boxes, a, a, 2, 70, w, 4.135, 1, a, a, None, None, a, 1,
+                                       G, 0.6, 80, a, a, a, a, a, a, None)
+
+    rc = refine(G=257)
+    assert rc < 0 and "at most 256" in _C.last_error()
+    rc = refine(boxes=ctypes.c_void_p(4096 + 4))
+    assert rc < 0 and "16-byte aligned" in _C.last_error()
+    rc = lib.d2mi_cascade_refine(a, a, a, a, 2, 70, w, 4.135, 1, None, a, None, None, a, 1, 5, 0.6,
+                                 80, a, a, a, a, a, a, None)
+    assert rc < 0 and "training mode needs" in _C.last_error()
+    rc = refine(G=0)
+    assert rc < 0 and "bad sizes" in _C.last_error()
+
+    def stages(n):
+        return lib.d2mi_fast_rcnn_inference_stages(a, a, a, a, n, a, a, a, a, 10, 2, 16, 3, 1, a, w,
+                                                   4.135, 0.05, 0.5, 10, a, a, a, a, a, a, 1 << 30,
+                                                   None)
+
+    for n in (0, 5):
+        rc = stages(n)
+        assert rc < 0 and "num_stages must be 1..4" in _C.last_error(), n
+    # the staged entry lays out the unstaged one's workspace: one byte short is refused
+    size = lib.d2mi_fast_rcnn_workspace_size(2, 16, 3, 0.05, 10)
+    rc = lib.d2mi_fast_rcnn_inference_stages(None, None, None, None, 3, None, None, None, None, 0,
+                                             2, 16, 3, 1, None, None, 4.135, 0.05, 0.5, 10, None,
+                                             None, None, None, None, a, size - 1, None)
+    assert rc < 0 and f"{size - 1} < {size}" in _C.last_error()
+
+
+def test_rpn_merge_entry_bound_without_gpu():
+    """d2mi_rpn_proposals admits L * post_nms_topk up to 16,320 merge entries
+    (the merge rank, the default) and refuses one more on the host."""
+    from detectron2_tensorflow_amd import _C
+    lib = _C.load()
+    rc = lib.d2mi_rpn_proposals(None, None, None, None, None, 5, 3, 2, None, 3265, 3265, 0.7, 0.0,
+                                None, 4.135, None, None, None, None, 0, None)
+    assert rc < 0 and "L*post_nms_topk=16325 exceeds 16320" in _C.last_error()
+
+
+def test_box_losses_outside_call_raises_a_clear_error():
+    _, model = _build(CASCADE)
+    with pytest.raises(RuntimeError, match="inside call"):
+        model.roi_heads._box_losses([], {"boxes": torch.zeros(1, 2, 4)})
