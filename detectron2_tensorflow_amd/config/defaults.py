@@ -3,11 +3,13 @@
 Key names and default values follow the reference's lib/config/defaults.py
 (:17-785) for every subtree the detection path reads (MODEL.* for
 GeneralizedRCNN / SingleStageDetector / PanopticFPN / SemanticSegmentor /
-ResNet / FPN / RPN / ROI heads / RetinaNet / SOLO / the semantic head, SOLVER,
-TRANSFORM, TEST, ...), so the reference YAML files merge without unknown-key
-errors.  Subsystems this build does not implement (SpineNet, YOLOv4, the
-panoptic evaluator, data augmentation, TFRecord readers) keep only the keys
-the shipped YAMLs set.
+ResNet / DarkNet53 / FPN / RPN / ROI heads / RetinaNet / SOLO / YOLOv4 / the
+semantic head, SOLVER, TRANSFORM, TEST, ...), so the reference YAML files
+merge without unknown-key errors.  MODEL.YOLOV4 (:671-682) is read by the
+YOLOv4 head, which runs inference only: CLS_NORMALIZER and IOU_NORMALIZER
+belong to its loss and are kept for the YAMLs.  Subsystems this build does
+not implement (SpineNet, the panoptic evaluator, data augmentation, TFRecord
+readers) keep only the keys the shipped YAMLs set.
 """
 from .config import CfgNode
 
@@ -94,6 +96,11 @@ def _tree():
             "SCORE_THRESH_TEST": 0.1, "UPDATE_SCORE_THRESH_TEST": 0.05, "MASK_THRESH_TEST": 0.5,
             "TOPK_CANDIDATES_TEST": 500, "NMS_KERNEL": "gaussian", "NMS_SIGMA": 2.0,
             "NMS_CLS_AGNOSTIC": False,
+        },
+        "YOLOV4": {
+            "CONV_DIMS": 256, "NORM": "BN", "ACTIVATION": "leaky_relu",
+            "SCALE_YX": [1.2, 1.1, 1.05], "CLS_NORMALIZER": 1.0, "IOU_NORMALIZER": 0.07,
+            "SCORE_THRESH_TEST": 0.05, "NMS_THRESH_TEST": 0.5,
         },
     }
     weight_decay = 0.0001

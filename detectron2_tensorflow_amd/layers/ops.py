@@ -2366,6 +2366,112 @@ def retinanet_inference(box_cls, box_delta, strides, cell_anchors, num_classes, 
     return ob, os_, oc, ov.bool()
 
 
+# -------------------------------------------------------------------- YOLOv4
+def yolo_host_arrays(level_hw, strides, cell_anchors, scale_yx):
+    """The host arrays of the two YOLOv4 entry points (d2mi.h): level_hw,
+    strides, the (h, w) of each [0, 0, h, w] cell anchor, and per level
+    (scale_yx, 0.5 * (scale_yx - 1)) formed in double as the reference's Python
+    scalars are.  Returns (lhw, strides, cell_hw, scale, L, A)."""
+    L = len(level_hw)
+    cells = [torch.as_tensor(c, dtype=torch.float32).reshape(-1, 4) for c in cell_anchors]
+    if len(cells) != L or len(strides) != L or len(scale_yx) != L:
+        raise ValueError("yolov4: one stride, cell-anchor set and scale_yx per level")
+    A = cells[0].shape[0]
+    if any(c.shape[0] != A for c in cells):
+        raise ValueError("yolov4: every level must have the same number of anchors")
+    lhw = _C.host_array(_C.ctypes.c_int32, [v for h, w in level_hw for v in (int(h), int(w))])
+    st = _C.host_array(_C.c_float, [float(s) for s in strides])
+    chw = _C.host_array(_C.c_float, [float(v) for c in cells for v in c[:, 2:].reshape(-1)])
+    sc = _C.host_array(_C.c_float, [v for s in scale_yx
+                                    for v in (float(s), 0.5 * (float(s) - 1))])
+    return lhw, st, chw, sc, L, A
+
+
+def _yolo_levels(pred_logits, num_classes, A):
+    logits = [_f32c(t) for t in pred_logits]
+    _C.require_device(*logits)
+    N = logits[0].shape[0]
+    for t in logits:
+        if t.dim() != 4 or t.shape[0] != N or t.shape[3] != A * (5 + int(num_classes)):
+            raise ValueError(f"yolov4: logits must be [N, H, W, A * (5 + K)], got {tuple(t.shape)}")
+    return logits, N
+
+
+def yolov4_predictions(pred_logits, strides, cell_anchors, scale_yx, num_classes):
+    """YOLOV4Outputs._get_predictions (yolov4_outputs.py:208-264), dense:
+    pred_logits[l] [N, H, W, A * (5 + K)] -> boxes [N, P, 4], conf [N, P],
+    score [N, P] (the max-class probability) and cls [N, P] int32."""
+    hw = [(t.shape[1], t.shape[2]) for t in pred_logits]
+    lhw, st, chw, sc, L, A = yolo_host_arrays(hw, strides, cell_anchors, scale_yx)
+    logits, N = _yolo_levels(pred_logits, num_classes, A)
+    P = sum(h * w for h, w in hw) * A
+    dev = logits[0].device
+    boxes = torch.empty((N, P, 4), dtype=torch.float32, device=dev)
+    conf = torch.empty((N, P), dtype=torch.float32, device=dev)
+    score = torch.empty((N, P), dtype=torch.float32, device=dev)
+    cls = torch.empty((N, P), dtype=torch.int32, device=dev)
+    rc = _C.lib().d2mi_yolov4_predictions(
+        _C.host_array(_C.c_void_p, [t.data_ptr() for t in logits]), lhw, st, chw, sc, L, A,
+        int(num_classes), N, _C.ptr(boxes), _C.ptr(conf), _C.ptr(score), _C.ptr(cls),
+        _C.stream_of(dev))
+    _C.check(rc, "d2mi_yolov4_predictions")
+    return boxes, conf, score, cls
+
+
+def yolov4_inference(pred_logits, strides, cell_anchors, scale_yx, num_classes, score_threshold,
+                     nms_threshold, max_detections):
+    """YOLOV4Outputs.inference (yolov4_outputs.py:331-390) fused
+    (d2mi_yolov4_inference): boxes [N, D, 4], scores [N, D], classes [N, D]
+    int32, is_valid [N, D] bool, D = max_detections."""
+    hw = [(t.shape[1], t.shape[2]) for t in pred_logits]
+    lhw, st, chw, sc, L, A = yolo_host_arrays(hw, strides, cell_anchors, scale_yx)
+    logits, N = _yolo_levels(pred_logits, num_classes, A)
+    dev = logits[0].device
+    ob = torch.empty((N, max_detections, 4), dtype=torch.float32, device=dev)
+    os_ = torch.empty((N, max_detections), dtype=torch.float32, device=dev)
+    oc = torch.empty((N, max_detections), dtype=torch.int32, device=dev)
+    ov = torch.empty((N, max_detections), dtype=torch.uint8, device=dev)
+    wsb = _C.lib().d2mi_yolov4_workspace_size(N, L, lhw, A)
+    ws = _C.workspace(wsb, dev)
+    ev = KernelTimer.start()
+    rc = _C.lib().d2mi_yolov4_inference(
+        _C.host_array(_C.c_void_p, [t.data_ptr() for t in logits]), lhw, st, chw, sc, L, A,
+        int(num_classes), N, float(score_threshold), float(nms_threshold), int(max_detections),
+        _C.ptr(ob), _C.ptr(os_), _C.ptr(oc), _C.ptr(ov), _C.ptr(ws), wsb, _C.stream_of(dev))
+    # algorithmic bytes: the dense logit read, 4 B per logit
+    KernelTimer.stop(ev, "yolov4_postprocess", 4 * sum(t.numel() for t in logits))
+    _C.check(rc, "d2mi_yolov4_inference")
+    return ob, os_, oc, ov.bool()
+
+
+def spp_pool(x):
+    """The SPP block's pools and concat (necks/yolov4.py:175-178) in one
+    launch: x [N, H, W, C] -> [N, H, W, 4C] = [pool13, pool9, pool5, x], the
+    pools stride 1 over the zero-padded map.  No autograd."""
+    x = _f32c(x)
+    _C.require_device(x)
+    N, H, W, C = x.shape
+    out = torch.empty((N, H, W, 4 * C), dtype=torch.float32, device=x.device)
+    rc = _C.lib().d2mi_spp_pool(_C.ptr(x), N, H, W, C, _C.ptr(out), _C.stream_of(x.device))
+    _C.check(rc, "d2mi_spp_pool")
+    return out
+
+
+ACT_LEAKY_RELU, ACT_MISH = 1, 2
+
+
+def activation_(x, code, alpha=0.0):
+    """In-place leaky_relu(alpha) (code ACT_LEAKY_RELU) or mish (ACT_MISH) over
+    a dense float32 tensor (d2mi_activation).  No autograd.  Returns x."""
+    _C.require_device(x)
+    if x.dtype is not torch.float32 or not x.is_contiguous():
+        raise ValueError("activation_: a contiguous float32 tensor")
+    rc = _C.lib().d2mi_activation(_C.ptr(x), x.numel(), int(code), float(alpha),
+                                  _C.stream_of(x.device))
+    _C.check(rc, "d2mi_activation")
+    return x
+
+
 # ------------------------------------------------------------- mask pasting
 def paste_masks(box_masks, boxes, out_shape, valid=None, yx_scale=None, threshold=0.5):
     """reframe_box_masks_to_image_masks (lib/structures/mask_ops.py:7-56) with

@@ -1,5 +1,6 @@
 """Model surface of lib/modeling: registries, build_model and the components."""
-from .anchor_generator import ANCHOR_GENERATOR_REGISTRY, DefaultAnchorGenerator, build_anchor_generator
+from .anchor_generator import (ANCHOR_GENERATOR_REGISTRY, DefaultAnchorGenerator,
+                               YOLOAnchorGenerator, build_anchor_generator)
 from .backbone import BACKBONE_REGISTRY, build_backbone
 from .box_regression import Box2BoxTransform
 from .meta_arch import (META_ARCH_REGISTRY, SEM_SEG_HEADS_REGISTRY, GeneralizedRCNN, PanopticFPN,

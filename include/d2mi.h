@@ -377,6 +377,47 @@ int d2mi_retinanet_inference(const float* const* cls, const float* const* box,
                              uint8_t* out_valid, void* workspace, size_t workspace_bytes,
                              void* stream);
 
+/* ----------------------------------------------------------------- YOLOv4
+ * Host arrays shared by the two entry points below: level_hw [L][2];
+ * strides [L]; cell_hw [L][A][2], the (h, w) of anchor_generator.py:240-243's
+ * [0, 0, height, width] cell anchors; scale_yx [L][2], MODEL.YOLOV4.SCALE_YX
+ * and 0.5 * (SCALE_YX - 1), each formed in double and rounded to f32 as the
+ * reference's Python scalars are.  logits[l] device [N, H_l, W_l, A*(5+K)],
+ * a row being (dy, dx, dh, dw, conf, K class logits).  The P = sum(H_l W_l A)
+ * predictions of an image are level-major, then (h, w, a).
+ *
+ * YOLOV4Outputs._get_predictions (yolov4_outputs.py:208-264) without the
+ * [N, P, K] probability tensor: out_boxes [N, P, 4] (no clamp, no clip),
+ * out_conf [N, P] = sigmoid(conf), out_score [N, P] = max_c(sigmoid(conf) *
+ * sigmoid(prob_c)), out_cls [N, P] the lowest class attaining it. */
+int d2mi_yolov4_predictions(const float* const* logits, const int32_t* level_hw,
+                            const float* strides, const float* cell_hw, const float* scale_yx,
+                            int L, int A, int K, int N, float* out_boxes, float* out_conf,
+                            float* out_score, int32_t* out_cls, void* stream);
+/* YOLOV4Outputs.inference (yolov4_outputs.py:331-390) per image: predictions
+ * with score > score_thresh in prediction order, class-agnostic
+ * NonMaxSuppressionV3 on the max-class scores (score descending, ties lowest
+ * index first, at most max_det <= 1000), gather, zero padding to max_det
+ * with out_valid 0.  The same decode / score functions as
+ * d2mi_yolov4_predictions.  Launches: score, compact, sort (1 - 3), NMS; no
+ * host synchronisation.  The workspace is linear in N * P. */
+size_t d2mi_yolov4_workspace_size(int N, int L, const int32_t* level_hw, int A);
+int d2mi_yolov4_inference(const float* const* logits, const int32_t* level_hw,
+                          const float* strides, const float* cell_hw, const float* scale_yx,
+                          int L, int A, int K, int N, float score_thresh, float nms_thresh,
+                          int max_det, float* out_boxes, float* out_scores, int32_t* out_classes,
+                          uint8_t* out_valid, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* SPP.call's three stride-1 max pools and concat (necks/yolov4.py:171-182;
+ * MaxPool2D pads with zeros, layers/wrappers.py:119-131, then pools VALID, so
+ * a tap outside the map counts as 0): x [N, H, W, C] -> out [N, H, W, 4C] =
+ * [pool13, pool9, pool5, x], C % 4 == 0, one launch. */
+int d2mi_spp_pool(const float* x, int N, int H, int W, int C, float* out, void* stream);
+/* In-place elementwise activation over n floats (lib/layers/activation.py):
+ * code 1 = leaky_relu(alpha) (:16-17), code 2 = mish, x * tanh(softplus(x))
+ * (:5-7). */
+int d2mi_activation(float* x, int64_t n, int code, float alpha, void* stream);
+
 /* ------------------------------------------------------------ Matrix NMS
  * lib/layers/nms.py:29-83 (SOLOv2 Matrix-NMS).  masks [M, HW] float,
  * classes int64 [M], scores [M], sum_masks [M] (nullable: computed);
