@@ -83,6 +83,9 @@ __device__ __forceinline__ float tf_iou(float4 a, float4 b) {
   return inter / ((area_i + area_j) - inter);
 }
 
+// tf.nn.sigmoid as the oracle states it (1 / (1 + exp(-x)), float32).
+__device__ __forceinline__ float sigmoidf_tf(float v) { return 1.f / (1.f + expf(-v)); }
+
 // Box2BoxTransform.apply_deltas for one (box, delta) pair
 // (lib/modeling/box_regression.py:95-122), float32, no contraction.
 // inv: wy, wx, wh, ww weights (division, as the reference divides).

@@ -1,6 +1,7 @@
 // Detection helpers shared by the proposal / post-processing translation
-// units (proposals.hip, topk.hip, retina_post.hip): per-level anchor geometry,
-// box-delta configuration, and the sigmoid-key search of the dense top-k.
+// units (proposals.hip, topk.hip, retina_post.hip, yolo.hip): per-level anchor
+// geometry, box-delta configuration, and the sigmoid-key search of the dense
+// top-k.
 #pragma once
 #include "internal.h"
 
@@ -40,9 +41,6 @@ struct DeltaCfg {
 int make_levels(Levels& lv, const float* const* a_ptrs, const float* const* b_ptrs,
                 const int32_t* level_hw, const float* strides, const float* cell, int L, int A);
 DeltaCfg make_dc(const float* w4, float clamp);
-
-// tf.nn.sigmoid as the oracle states it (1 / (1 + exp(-x)), float32).
-__device__ __forceinline__ float sigmoidf_tf(float v) { return 1.f / (1.f + expf(-v)); }
 
 constexpr uint32_t kKeyNegInf = 0x007fffffu;  // orderable(-inf)
 constexpr uint32_t kKeyPosInf = 0xff800000u;  // orderable(+inf)

@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "wave.h"
 
 namespace d2mi {
 namespace {
@@ -173,17 +174,11 @@ struct GnLevels {
   int L;
 };
 
-__device__ __forceinline__ int gn_level_of(const int* first, int L, int i) {
-  int l = 0;
-  while (l + 1 < L && i >= first[l + 1]) ++l;
-  return l;
-}
-
 __global__ __launch_bounds__(kGnThreads) void gn_sum_levels_kernel(GnLevels lv, int C, int G,
                                                                   const float* __restrict__ mean,
                                                                   float* __restrict__ partial) {
   __shared__ float red[kGnThreads];
-  const int l = gn_level_of(lv.wg0, lv.L, blockIdx.x);
+  const int l = level_of(lv.wg0, lv.L, (int)blockIdx.x);
   const int local = blockIdx.x - lv.wg0[l];
   const int chunks = lv.chunks[l];
   const int n = local / chunks, chunk = local - n * chunks;
@@ -225,7 +220,7 @@ __global__ __launch_bounds__(kGnThreads) void gn_sum_levels_kernel(GnLevels lv, 
 __global__ void gn_reduce_levels_kernel(GnLevels lv, const float* __restrict__ partial, int G,
                                         float* __restrict__ out) {
   const int row = blockIdx.x;
-  const int l = gn_level_of(lv.st0, lv.L, row);
+  const int l = level_of(lv.st0, lv.L, row);
   const int n = row - lv.st0[l];
   const int chunks = lv.chunks[l];
   const size_t base = (size_t)lv.wg0[l] + (size_t)n * chunks;

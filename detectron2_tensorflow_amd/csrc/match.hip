@@ -16,6 +16,7 @@
 #include "common.h"
 #include "internal.h"
 #include "iou.h"
+#include "wave.h"
 
 namespace d2mi {
 namespace {
@@ -27,6 +28,7 @@ constexpr int kMaxGt = 256;
 // 4 before: 263 atomics per GT per image at 1333x800)
 constexpr int kBestPer = 16;
 
+// (not common.h's orderable / from_orderable: these keep -0.0 below +0.0)
 __device__ __forceinline__ unsigned ord(float f) {
   const unsigned u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -91,7 +93,7 @@ __global__ __launch_bounds__(256) void best_gt_kernel(const float4* __restrict__
 #pragma unroll
     for (int k = 0; k < kPer; ++k)
       if (ok[k]) m = fmaxf(m, iou_of(g_s[g], b[k]));
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = wave_max(m);
     if (lane == 0) red[wv] = m;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -21,6 +21,7 @@
 // IoU is the float32 expression of TF's IOU() in the same evaluation order
 // (compiled with -ffp-contract=off), so the kept indices are bit-exact.
 #include "internal.h"
+#include "wave.h"
 
 namespace d2mi {
 namespace {
@@ -125,12 +126,6 @@ __global__ __launch_bounds__(64 * kMaskWaves) void nms_mask_kernel(
     if (lane < rmax) mask[(base + row0 + lane) * T + ct] = mine;
     if (want_col) colw[(((size_t)s * T + rt) * 2 + (ct - rt)) * 64 + lane] = colword;
   }
-}
-
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
-  const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)v, l);
-  const uint32_t hi = __builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
-  return ((uint64_t)hi << 32) | lo;
 }
 
 // One workgroup of four waves per segment; removed[] lives in LDS (T words).

@@ -14,6 +14,7 @@
 // fixed-order sum: deterministic, no atomics) and updates its chunk.
 #include "common.h"
 #include "internal.h"
+#include "wave.h"
 
 namespace d2mi {
 namespace {
@@ -35,17 +36,6 @@ struct SgdChunk {
   int pad;
   long long begin, end;
 };
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float s = 0.f;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += red[i];
-  return s;  // valid in thread 0
-}
 
 // float4 body when every pointer of the tensor is 16-B aligned (chunk
 // boundaries are multiples of kChunk), scalar tail; 4 vectors in flight per

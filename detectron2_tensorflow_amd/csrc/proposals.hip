@@ -13,6 +13,7 @@
 // selecting first and decoding only the selected anchors (regenerated from
 // the flat index) gives identical results for a fraction of the traffic.
 #include "detect.h"
+#include "wave.h"
 
 namespace d2mi {
 namespace {
@@ -329,15 +330,6 @@ __global__ void slot_map_kernel(const int32_t* roi_img, const int32_t* roi_slot,
     return;
   }
   slot2roi[n * P + s] = r;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // One wave per ROI: softmax over K+1 logits, class-specific decode + clip,

@@ -16,26 +16,27 @@
 // p (1 - p), d pow = gamma (1 - p_t)^(gamma - 1)), times the upstream
 // gradients read from the device.  Memory-bound: one read of the logits
 // forward, one read + one write backward.
-#include "common.h"
+#include "box_loss.h"
+#include "wave.h"
 
 namespace d2mi {
 namespace {
 
-constexpr int kMaxRetinaLevels = 8;
+static_assert(D2MI_MAX_LEVELS == 8, "RetinaLossArgs is a kernel argument: its layout is fixed");
 
 struct RetinaLossArgs {
-  const float* cls[kMaxRetinaLevels];    // [N, HW_l, A*K]
-  const float* box[kMaxRetinaLevels];    // [N, HW_l, A*4]
-  float* dcls[kMaxRetinaLevels];
-  float* dbox[kMaxRetinaLevels];
-  long long abase[kMaxRetinaLevels + 1];  // first anchor index of each level (per image)
+  const float* cls[D2MI_MAX_LEVELS];     // [N, HW_l, A*K]
+  const float* box[D2MI_MAX_LEVELS];     // [N, HW_l, A*4]
+  float* dcls[D2MI_MAX_LEVELS];
+  float* dbox[D2MI_MAX_LEVELS];
+  long long abase[D2MI_MAX_LEVELS + 1];  // first anchor index of each level (per image)
   int L, N, K, A, G;
-  long long R;                            // anchors per image
-  const float4* anchors;                  // [R]
-  const float4* gt;                       // [N, G]
-  const long long* gt_classes;            // [N, G]
-  const long long* matches;               // [N, R]
-  const long long* labels;                // [N, R]: 1 fg, 0 bg, -1 ignore
+  long long R;                           // anchors per image
+  const float4* anchors;                 // [R]
+  const float4* gt;                      // [N, G]
+  const long long* gt_classes;           // [N, G]
+  const long long* matches;              // [N, R]
+  const long long* labels;               // [N, R]: 1 fg, 0 bg, -1 ignore
   float alpha, gamma, beta;
   float wy, wx, wh, ww;
 };
@@ -49,7 +50,8 @@ __device__ __forceinline__ long long class_of(const RetinaLossArgs& a, int n, lo
   return a.gt_classes[(size_t)n * a.G + a.matches[(size_t)n * a.R + r]];
 }
 
-__device__ __forceinline__ void level_of(const RetinaLossArgs& a, long long r, int& l) {
+// wave.h's level_of over abase, spelled out (the call compiled to other code here)
+__device__ __forceinline__ void anchor_level(const RetinaLossArgs& a, long long r, int& l) {
   l = 0;
   while (l + 1 < a.L && r >= a.abase[l + 1]) ++l;
 }
@@ -58,7 +60,7 @@ __device__ __forceinline__ float focal(float x, float t, float alpha, float gamm
   // sigmoid_focal_loss (loss.py:86-95): p = sigmoid(x); ce =
   // sigmoid_cross_entropy_with_logits (max(x, 0) - x t + log1p(exp(-|x|)));
   // p_t = p t + (1 - p)(1 - t); ce (1 - p_t)^gamma, times alpha_t
-  const float p = 1.f / (1.f + expf(-x));
+  const float p = sigmoidf_tf(x);
   const float ce = (fmaxf(x, 0.f) - x * t) + log1pf(expf(-fabsf(x)));
   const float pt = p * t + (1.f - p) * (1.f - t);
   float loss = ce * powf(1.f - pt, gamma);
@@ -67,7 +69,7 @@ __device__ __forceinline__ float focal(float x, float t, float alpha, float gamm
 }
 
 __device__ __forceinline__ float focal_grad(float x, float t, float alpha, float gamma) {
-  const float p = 1.f / (1.f + expf(-x));
+  const float p = sigmoidf_tf(x);
   const float ce = (fmaxf(x, 0.f) - x * t) + log1pf(expf(-fabsf(x)));
   const float pt = p * t + (1.f - p) * (1.f - t);
   const float q = 1.f - pt;
@@ -82,26 +84,8 @@ __device__ __forceinline__ float focal_grad(float x, float t, float alpha, float
 }
 
 __device__ __forceinline__ float4 target_of(const RetinaLossArgs& a, int n, long long r) {
-  const float4 s = a.anchors[r];
-  const float4 t = a.gt[(size_t)n * a.G + a.matches[(size_t)n * a.R + r]];
-  const float sh = s.z - s.x, sw = s.w - s.y;
-  const float scy = s.x + 0.5f * sh, scx = s.y + 0.5f * sw;
-  const float th = t.z - t.x, tw = t.w - t.y;
-  const float tcy = t.x + 0.5f * th, tcx = t.y + 0.5f * tw;
-  return make_float4(a.wy * (tcy - scy) / sh, a.wx * (tcx - scx) / sw, a.wh * logf(th / sh),
-                     a.ww * logf(tw / sw));
-}
-
-__device__ __forceinline__ float sl1(float t, float p, float beta) {
-  const float d = fabsf(p - t);
-  return beta < 1e-5f ? d : (d < beta ? 0.5f * (d * d) / beta : d - 0.5f * beta);
-}
-
-__device__ __forceinline__ float sl1_grad(float t, float p, float beta) {
-  const float d = p - t;
-  const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-  if (beta < 1e-5f) return sg;
-  return fabsf(d) < beta ? d / beta : sg;
+  return box_deltas(a.anchors[r], a.gt[(size_t)n * a.G + a.matches[(size_t)n * a.R + r]], a.wy,
+                    a.wx, a.wh, a.ww);
 }
 
 // grid (blocks, N): the image's R*K/4 logit float4s (every level), then its
@@ -119,7 +103,7 @@ __global__ __launch_bounds__(256) void retina_loss_fwd_kernel(RetinaLossArgs a,
     const long long c = class_of(a, n, r);
     if (c < 0) continue;
     int l;
-    level_of(a, r, l);
+    anchor_level(a, r, l);
     const long long lr = r - a.abase[l];
     const long long per = (a.abase[l + 1] - a.abase[l]) * a.K;  // level elements per image
     const float4 x = *reinterpret_cast<const float4*>(a.cls[l] + (size_t)n * per + lr * a.K + k0);
@@ -131,7 +115,7 @@ __global__ __launch_bounds__(256) void retina_loss_fwd_kernel(RetinaLossArgs a,
   for (long long r = blockIdx.x * 256ll + threadIdx.x; r < a.R; r += gridDim.x * 256ll) {
     if (a.labels[(size_t)n * a.R + r] != 1) continue;
     int l;
-    level_of(a, r, l);
+    anchor_level(a, r, l);
     const long long lr = r - a.abase[l];
     const long long per = (a.abase[l + 1] - a.abase[l]) * 4;
     const float4 d = *reinterpret_cast<const float4*>(a.box[l] + (size_t)n * per + lr * 4);
@@ -139,21 +123,8 @@ __global__ __launch_bounds__(256) void retina_loss_fwd_kernel(RetinaLossArgs a,
     box += ((sl1(t.x, d.x, a.beta) + sl1(t.y, d.y, a.beta)) + sl1(t.z, d.z, a.beta)) +
            sl1(t.w, d.w, a.beta);
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    cls += __shfl_down(cls, o, 64);
-    box += __shfl_down(box, o, 64);
-  }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) red[wv] = make_float2(cls, box);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float2 s = red[0];
-    for (int k = 1; k < 4; ++k) {
-      s.x += red[k].x;
-      s.y += red[k].y;
-    }
-    part[(size_t)n * gridDim.x + blockIdx.x] = s;
-  }
+  const float2 s = block_sum(make_float2(cls, box), red);
+  if (threadIdx.x == 0) part[(size_t)n * gridDim.x + blockIdx.x] = s;
 }
 
 // every element of every d_cls / d_box level written (0 where it does not count)
@@ -170,7 +141,7 @@ __global__ __launch_bounds__(256) void retina_loss_bwd_kernel(RetinaLossArgs a,
     const int k0 = (int)(i - r * K4) * 4;
     const long long c = class_of(a, n, r);
     int l;
-    level_of(a, r, l);
+    anchor_level(a, r, l);
     const long long lr = r - a.abase[l];
     const size_t off = (size_t)n * (a.abase[l + 1] - a.abase[l]) * a.K + lr * a.K + k0;
     float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -185,7 +156,7 @@ __global__ __launch_bounds__(256) void retina_loss_bwd_kernel(RetinaLossArgs a,
   }
   for (long long r = blockIdx.x * 256ll + threadIdx.x; r < a.R; r += gridDim.x * 256ll) {
     int l;
-    level_of(a, r, l);
+    anchor_level(a, r, l);
     const long long lr = r - a.abase[l];
     const size_t off = (size_t)n * (a.abase[l + 1] - a.abase[l]) * 4 + lr * 4;
     float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -207,7 +178,7 @@ int make_args(RetinaLossArgs& a, const float* const* cls, const float* const* bo
               const long long* gt_classes, int G, const long long* matches,
               const long long* labels, float alpha, float gamma, float beta,
               const float* weights) {
-  D2MI_REQUIRE(L >= 1 && L <= kMaxRetinaLevels, "retina loss: 1..8 levels");
+  D2MI_REQUIRE(L >= 1 && L <= D2MI_MAX_LEVELS, "retina loss: 1..8 levels");
   D2MI_REQUIRE(N > 0 && K > 0 && K % 4 == 0 && A > 0 && G > 0, "retina loss: bad shape (K %% 4)");
   D2MI_REQUIRE(((uintptr_t)anchors & 15) == 0 && ((uintptr_t)gt_boxes & 15) == 0,
                "retina loss: 16-byte aligned anchors / GT boxes");

@@ -36,6 +36,7 @@
 // of the unfused pipeline (topk.hip, nms.hip, proposals.hip), which stays
 // selectable with the tuning key "retina_fused" = 0.
 #include "detect.h"
+#include "wave.h"
 
 namespace d2mi {
 namespace {
@@ -743,6 +744,7 @@ __device__ uint32_t wg_kth_smallest(const uint32_t (&h)[8], const bool (&ok)[8],
     mn = min(mn, lane_xor32<1>(mn));
     mx = max(mx, lane_xor32<1>(mx));
   } else {
+    // (wave_min and wave_max of wave.h, kept as one interleaved loop)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       mn = min(mn, (uint32_t)__shfl_xor((int)mn, o));
@@ -1061,8 +1063,7 @@ __global__ __launch_bounds__(kWG) void retina_finish_kernel(
   // per-wave max, one atomic per wave with a kept box
   const int lane = t & 63;
   uint32_t wm = any ? mymax : 0u;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) wm = max(wm, (uint32_t)__shfl_xor((int)wm, o));
+  wm = wave_max(wm);
   if (__ballot(any) != 0 && lane == 0) atomicMax(&maxc[n], wm);
   if (kept) atomicAdd(&s_cnt, kept);
   __syncthreads();
@@ -1086,12 +1087,6 @@ __global__ __launch_bounds__(kWG) void retina_finish_kernel(
 }
 
 // -------------------------------------------------------------------- nms
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
-  const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)v, l);
-  const uint32_t hi = __builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
-  return ((uint64_t)hi << 32) | lo;
-}
-
 // Merge rank of the per-level sorted candidate lists of one image, many
 // workgroups per image (one candidate per thread): position = own rank +
 // earlier levels' scores >= s + later levels' scores > s (the concat

@@ -17,32 +17,11 @@
 // Element formulas: the CE as log-softmax (x_c - max) - log(sum exp(x - max)),
 // get_deltas as box_regression.py:38-74, smooth-L1 as layers/loss.py, the
 // BCE as ATen's binary_cross_entropy_with_logits.
-#include "common.h"
+#include "box_loss.h"
+#include "wave.h"
 
 namespace d2mi {
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-__device__ __forceinline__ float sl1(float t, float p, float beta) {
-  const float d = fabsf(t - p);
-  return beta < 1e-5f ? d : (d < beta ? 0.5f * (d * d) / beta : d - 0.5f * beta);
-}
-
-__device__ __forceinline__ float sl1_grad(float t, float p, float beta) {
-  const float d = p - t;
-  const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-  if (beta < 1e-5f) return sg;
-  return fabsf(d) < beta ? d / beta : sg;
-}
 
 struct FrcnArgs {
   const float* logits;          // [B, K1]
@@ -56,13 +35,7 @@ struct FrcnArgs {
 };
 
 __device__ __forceinline__ float4 frcn_target(const FrcnArgs& a, int r) {
-  const float4 s = a.proposals[r], t = a.gt_boxes[r];
-  const float sh = s.z - s.x, sw = s.w - s.y;
-  const float scy = s.x + 0.5f * sh, scx = s.y + 0.5f * sw;
-  const float th = t.z - t.x, tw = t.w - t.y;
-  const float tcy = t.x + 0.5f * th, tcx = t.y + 0.5f * tw;
-  return make_float4(a.wy * (tcy - scy) / sh, a.wx * (tcx - scx) / sw, a.wh * logf(th / sh),
-                     a.ww * logf(tw / sw));
+  return box_deltas(a.proposals[r], a.gt_boxes[r], a.wy, a.wx, a.wh, a.ww);
 }
 
 // row class (where(valid, gt, 0)), foreground flag, regression column
@@ -193,11 +166,6 @@ __device__ __forceinline__ int mask_channel(const MaskArgs& a, int r) {
   return (int)(c < 0 ? 0 : (c > a.C - 1 ? a.C - 1 : c));
 }
 
-__device__ __forceinline__ float bce(float x, float z) {
-  const float m = fmaxf(-x, 0.f);
-  return (1.f - z) * x + m + logf(expf(-m) + expf(-x - m));
-}
-
 // one wave per row: terms[r] = (BCE sum over the map, fg)
 __global__ __launch_bounds__(256) void mask_loss_rows_kernel(MaskArgs a, float* __restrict__ terms) {
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -209,7 +177,7 @@ __global__ __launch_bounds__(256) void mask_loss_rows_kernel(MaskArgs a, float* 
     const int c = mask_channel(a, r);
     const float* x = a.logits + (size_t)r * a.P * a.C + c;
     const float* z = a.target + (size_t)r * a.P;
-    for (int p = lane; p < a.P; p += 64) s += bce(x[(size_t)p * a.C], z[p]);
+    for (int p = lane; p < a.P; p += 64) s += bce_logits(x[(size_t)p * a.C], z[p]);
     s = wave_sum(s);
   }
   if (lane == 0) {
@@ -237,8 +205,7 @@ __global__ __launch_bounds__(256) void mask_loss_bwd_kernel(MaskArgs a, const fl
     if (a.fg[r]) {
       const int c = mask_channel(a, r);
       if (c >= c0 && c < c0 + W) {
-        const float x = a.logits[rp * a.C + c], z = a.target[rp];
-        v[c - c0] = g * (1.f / (1.f + expf(-x)) - z);
+        v[c - c0] = g * bce_logits_grad(a.logits[rp * a.C + c], a.target[rp]);
       }
     }
     if (VEC4)

@@ -13,6 +13,7 @@
 //                         index gathers, a sum), 4-28 us each.
 // Pure data movement and comparisons: the outputs are the same values.
 #include "common.h"
+#include "wave.h"
 
 namespace d2mi {
 namespace {
@@ -75,8 +76,7 @@ __global__ __launch_bounds__(kTakeT) void roi_sample_take_kernel(
     const size_t p = (size_t)n * M + order[q];
     mine += (valid[q] && gt_classes[p] < K) ? 1 : 0;
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) mine += __shfl_xor(mine, d);
+  mine = wave_sum(mine);
   if (lane == 0) s_wave[w] = mine;
   if (t == 0) s_run = 0;
   __syncthreads();

@@ -10,7 +10,8 @@
 // (g_cls, g_loc) read from the device (no host synchronisation).
 // Element formulas follow ATen's binary_cross_entropy_with_logits and the
 // smooth_l1_loss of layers/loss.py.
-#include "common.h"
+#include "box_loss.h"
+#include "wave.h"
 
 namespace d2mi {
 namespace {
@@ -28,26 +29,8 @@ struct RpnLossArgs {
 };
 
 __device__ __forceinline__ float4 target_of(const RpnLossArgs& a, int n, int p) {
-  const float4 s = a.anchors[p];
-  const float4 t = a.gt[(size_t)n * a.G + (int)a.matches[(size_t)n * a.P + p]];
-  const float sh = s.z - s.x, sw = s.w - s.y;
-  const float scy = s.x + 0.5f * sh, scx = s.y + 0.5f * sw;
-  const float th = t.z - t.x, tw = t.w - t.y;
-  const float tcy = t.x + 0.5f * th, tcx = t.y + 0.5f * tw;
-  return make_float4(a.wy * (tcy - scy) / sh, a.wx * (tcx - scx) / sw, a.wh * logf(th / sh),
-                     a.ww * logf(tw / sw));
-}
-
-__device__ __forceinline__ float sl1(float t, float p, float beta) {
-  const float d = fabsf(t - p);
-  return beta < 1e-5f ? d : (d < beta ? 0.5f * (d * d) / beta : d - 0.5f * beta);
-}
-
-__device__ __forceinline__ float sl1_grad(float t, float p, float beta) {
-  const float d = p - t;  // d|t - p| / dp = sign(p - t)
-  const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-  if (beta < 1e-5f) return sg;
-  return fabsf(d) < beta ? d / beta : sg;
+  return box_deltas(a.anchors[p], a.gt[(size_t)n * a.G + (int)a.matches[(size_t)n * a.P + p]],
+                    a.wy, a.wx, a.wh, a.ww);
 }
 
 __global__ __launch_bounds__(256) void rpn_loss_fwd_kernel(RpnLossArgs a, float2* __restrict__ part) {
@@ -56,32 +39,15 @@ __global__ __launch_bounds__(256) void rpn_loss_fwd_kernel(RpnLossArgs a, float2
   float cls = 0.f, loc = 0.f;
   for (int p = blockIdx.x * 256 + threadIdx.x; p < a.P; p += gridDim.x * 256) {
     const size_t i = (size_t)n * a.P + p;
-    if (a.samp[i]) {
-      const float x = a.logits[i], z = a.pos[i] ? 1.f : 0.f;
-      const float m = fmaxf(-x, 0.f);
-      cls += (1.f - z) * x + m + logf(expf(-m) + expf(-x - m));
-    }
+    if (a.samp[i]) cls += bce_logits(a.logits[i], a.pos[i] ? 1.f : 0.f);
     if (a.pos[i]) {
       const float4 t = target_of(a, n, p), d = a.deltas[i];
       loc += ((sl1(t.x, d.x, a.beta) + sl1(t.y, d.y, a.beta)) + sl1(t.z, d.z, a.beta)) +
              sl1(t.w, d.w, a.beta);
     }
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    cls += __shfl_down(cls, o, 64);
-    loc += __shfl_down(loc, o, 64);
-  }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) red[wv] = make_float2(cls, loc);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float2 s = red[0];
-    for (int k = 1; k < 4; ++k) {
-      s.x += red[k].x;
-      s.y += red[k].y;
-    }
-    part[(size_t)n * gridDim.x + blockIdx.x] = s;
-  }
+  const float2 s = block_sum(make_float2(cls, loc), red);
+  if (threadIdx.x == 0) part[(size_t)n * gridDim.x + blockIdx.x] = s;
 }
 
 // g_cls / g_loc: device scalars (null: a zero gradient), times `scale`
@@ -99,10 +65,7 @@ __global__ __launch_bounds__(256) void rpn_loss_bwd_kernel(RpnLossArgs a,
   for (int p = blockIdx.x * 256 + threadIdx.x; p < a.P; p += gridDim.x * 256) {
     const size_t i = (size_t)n * a.P + p;
     float dl = 0.f;
-    if (a.samp[i]) {
-      const float x = a.logits[i], z = a.pos[i] ? 1.f : 0.f;
-      dl = g_cls * (1.f / (1.f + expf(-x)) - z);
-    }
+    if (a.samp[i]) dl = g_cls * bce_logits_grad(a.logits[i], a.pos[i] ? 1.f : 0.f);
     d_logits[i] = dl;
     float4 dd = make_float4(0.f, 0.f, 0.f, 0.f);
     if (a.pos[i]) {
@@ -195,18 +158,18 @@ extern "C" int d2mi_rpn_loss_bwd(const float* logits, const float* deltas, const
 // ------------------------------------------------ RPN head output layout
 namespace d2mi {
 namespace {
-constexpr int kMaxHeadLevels = 8;
+static_assert(D2MI_MAX_LEVELS == 8, "HeadLevels is a kernel argument: its layout is fixed");
 struct HeadLevels {
-  const float* y[kMaxHeadLevels];
-  float* gy[kMaxHeadLevels];
-  int t0[kMaxHeadLevels + 1];  // first pixel of level l in the concatenation
+  const float* y[D2MI_MAX_LEVELS];
+  float* gy[D2MI_MAX_LEVELS];
+  int t0[D2MI_MAX_LEVELS + 1];  // first pixel of level l in the concatenation
   int L;
 };
 
 __device__ __forceinline__ int head_level(const HeadLevels& h, int t) {
   int l = 0;
 #pragma unroll
-  for (int i = 1; i < kMaxHeadLevels; ++i)
+  for (int i = 1; i < D2MI_MAX_LEVELS; ++i)
     if (i < h.L && t >= h.t0[i]) l = i;
   return l;
 }
@@ -308,7 +271,7 @@ __global__ __launch_bounds__(256) void rpn_head_scatter4_kernel(HeadLevels h, in
 }
 
 int head_levels(HeadLevels& h, const int32_t* hw, int L) {
-  D2MI_REQUIRE(L >= 1 && L <= kMaxHeadLevels, "RPN head: %d levels (1..%d)", L, kMaxHeadLevels);
+  D2MI_REQUIRE(L >= 1 && L <= D2MI_MAX_LEVELS, "RPN head: %d levels (1..%d)", L, D2MI_MAX_LEVELS);
   h.L = L;
   h.t0[0] = 0;
   for (int l = 0; l < L; ++l) {

@@ -28,13 +28,14 @@
 
 #include "common.h"
 #include "resize.h"
+#include "wave.h"
 
 namespace d2mi {
 namespace {
 
 constexpr int kTile = 8;
 constexpr int kHalo = kTile + 2;
-constexpr int kThreads = 256;
+constexpr int kThreads = 256;  // (block_sum's four waves)
 constexpr int kMaxScale = 8;
 constexpr size_t kMaxLds = 64 * 1024;
 
@@ -106,20 +107,6 @@ __device__ __forceinline__ int label_at(const int32_t* __restrict__ labels, int 
   if (oy >= Hl || ox >= Wl || oy >= shapes[2 * n] || ox >= shapes[2 * n + 1]) return -1;
   const int l = labels[((size_t)n * Hl + oy) * Wl + ox];
   return (l == ignore_value || l < 0 || l >= C) ? -1 : l;
-}
-
-// Fixed-order sum over the workgroup; the result is valid in thread 0.
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* red) {
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) red[wave] = v;
-  __syncthreads();
-  T r = 0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < kThreads / 64; ++i) r += red[i];
-  __syncthreads();
-  return r;
 }
 
 __global__ __launch_bounds__(kThreads) void seg_loss_fwd_kernel(
@@ -472,6 +459,7 @@ __global__ __launch_bounds__(kThreads) void pan_step_kernel(PanArgs a, int k) {
   }
   if (m_count) {
     const int ba = block_sum(area, red_i);
+    __syncthreads();  // (red_i reused)
     const int bi = block_sum(inter, red_i);
     if (threadIdx.x == 0 && ba > 0) {
       atomicAdd(&a.ws.area[n * a.D + k], ba);

@@ -37,6 +37,7 @@
 #include "common.h"
 #include "internal.h"
 #include "resize.h"
+#include "wave.h"
 
 namespace d2mi {
 namespace {
@@ -79,23 +80,15 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __res
   }
 }
 
-__device__ __forceinline__ float sigmoidf_tf(float v) { return 1.f / (1.f + expf(-v)); }
-
 // --------------------------------------------------------------- level table
-constexpr int kMaxLevels = 8;
+static_assert(D2MI_MAX_LEVELS == 8, "SoloLevels is a kernel argument: its layout is fixed");
 struct SoloLevels {
-  const float* cate[kMaxLevels];  // [N, S, S, K] logits
-  int S[kMaxLevels];
-  int off[kMaxLevels + 1];        // first cell of each level; off[L] = T
-  float stride[kMaxLevels];
+  const float* cate[D2MI_MAX_LEVELS];  // [N, S, S, K] logits
+  int S[D2MI_MAX_LEVELS];
+  int off[D2MI_MAX_LEVELS + 1];        // first cell of each level; off[L] = T
+  float stride[D2MI_MAX_LEVELS];
   int L;
 };
-
-__device__ __forceinline__ int level_of(const SoloLevels& lv, int c) {
-  int l = 0;
-  while (l + 1 < lv.L && c >= lv.off[l + 1]) ++l;
-  return l;
-}
 
 // ------------------------------------------------------------------- stage 1
 // One wave per (image, cell): sigmoid of the cell's K logits and of its up,
@@ -111,7 +104,7 @@ __global__ __launch_bounds__(256) void solo_cells_kernel(SoloLevels lv, int N, i
   const int lane = threadIdx.x & 63;
   if (wave >= N * T) return;
   const int n = wave / T, c = wave % T;
-  const int l = level_of(lv, c);
+  const int l = level_of(lv.off, lv.L, c);
   const int S = lv.S[l];
   const int loc = c - lv.off[l];
   const int i = loc / S, j = loc % S;
@@ -252,7 +245,7 @@ __global__ __launch_bounds__(256) void solo_cand_kernel(
     const float p = probs[e];
     const int gr = row_off[n] + row;
     const float sm = sum_masks[gr];
-    const float stride = lv.stride[level_of(lv, c)];
+    const float stride = lv.stride[level_of(lv.off, lv.L, c)];
     if (p > thr && sm > stride) {
       valid = true;
       out = p * (sum_scores[gr] / sm);
@@ -577,7 +570,7 @@ __global__ __launch_bounds__(256) void solo_inter_reduce_kernel(
     for (int jl = wv; jl < kRedCols; jl += 4) {
       float mx = tile[jl][lane];
       if (TS > 64) mx = fmaxf(mx, tile[jl][64 + lane]);
-      for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+      mx = wave_max(mx);
       const int j = tj * TS + cb * kRedCols + jl;
       if (lane == 0 && j < k && mx > 0.f)
         atomicMax(reinterpret_cast<int*>(comp) + (size_t)n * k + j, __float_as_int(mx));
@@ -612,7 +605,7 @@ __global__ __launch_bounds__(256) void solo_decay_rows_kernel(
     const float d = kernel == 0 ? expf(ns * (v * v - ci * ci)) : (1.f - v) / (1.f - ci);
     mn = fminf(mn, d);
   }
-  for (int o = 32; o > 0; o >>= 1) mn = fminf(mn, __shfl_xor(mn, o));
+  mn = wave_min(mn);
   if (lane == 0) out[row] = scores[row] * mn;
 }
 
@@ -726,19 +719,6 @@ __global__ __launch_bounds__(512) void solo_keep_kernel(
     if (threadIdx.x == 0) base_sh += total;
     __syncthreads();
   }
-}
-
-__device__ __forceinline__ int wave_min(int v) {
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 __device__ __forceinline__ float mask_bit(const uint64_t* m, size_t p) {
@@ -966,7 +946,7 @@ __global__ __launch_bounds__(64) void solo_boxes_kernel(const BoxAcc* __restrict
 
 static int fill_levels(SoloLevels& lv, const float* const* cate, const int32_t* grids,
                        const float* strides, int L) {
-  D2MI_REQUIRE(L >= 1 && L <= kMaxLevels, "SOLO: 1..%d levels (got %d)", kMaxLevels, L);
+  D2MI_REQUIRE(L >= 1 && L <= D2MI_MAX_LEVELS, "SOLO: 1..%d levels (got %d)", D2MI_MAX_LEVELS, L);
   lv.L = L;
   lv.off[0] = 0;
   for (int l = 0; l < L; ++l) {

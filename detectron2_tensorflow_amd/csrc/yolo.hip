@@ -29,6 +29,7 @@
 // The decode, sigmoid, score and class expressions of the two YOLO entry
 // points are the same __device__ functions, so their bits agree.
 #include "detect.h"
+#include "wave.h"
 
 namespace d2mi {
 namespace {
@@ -200,8 +201,7 @@ __global__ __launch_bounds__(kYB) void yolo_compact_kernel(int P, int nb,
   // survivors of the image's earlier blocks
   int before = 0;
   for (int i = t; i < b; i += kYB) before += bcnt[n * nb + i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o);
+  before = wave_sum(before);
   const int p = b * kYB + t;
   const uint64_t key = p < P ? keys[(size_t)n * P + p] : ~0ull;
   const bool keep = key != ~0ull;
@@ -227,12 +227,6 @@ __global__ __launch_bounds__(kYB) void yolo_compact_kernel(int P, int nb,
 }
 
 // --------------------------------------------------------------------- nms
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
-  const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)v, l);
-  const uint32_t hi = __builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
-  return ((uint64_t)hi << 32) | lo;
-}
-
 // Greedy NonMaxSuppressionV3 of image n's sorted candidates (the NMS phase of
 // retina_post.hip without class offsets): a tile's 64 candidates are tested
 // against the kept list by all 16 waves (kept rows dealt round the waves),

@@ -535,6 +535,72 @@ def test_fused_fast_rcnn_loss_matches_tensor_formulation(dev, nreg):
     torch.testing.assert_close(a[3], b[3], rtol=1e-5, atol=1e-8)
 
 
+def test_three_training_losses_evaluate_one_box_regression_formula(dev):
+    """ops.rpn_loss, ops.fast_rcnn_loss (class-agnostic and class-specific) and
+    ops.retina_loss, each fed the same (source box, GT box, predicted deltas,
+    weights, beta) as its only positive row, give the same box loss and the
+    same delta gradient to the bit: the three kernels evaluate the get_deltas
+    and smooth-L1 of csrc/box_loss.h.  One positive row makes every reduction
+    a sum with zeros, and max(1, #valid) = 1 makes the Fast R-CNN normaliser
+    exact, so no tolerance is involved."""
+    from detectron2_tensorflow_amd.layers import ops
+    g = torch.Generator().manual_seed(11)
+    A, K = 4, 4  # RPN anchors / RetinaNet anchors of the one cell; classes (K % 4 == 0)
+    t = lambda a: a.to(dev)
+    for case in range(32):
+        weights = ((10.0, 10.0, 5.0, 5.0), (1.0, 1.0, 1.0, 1.0))[case % 2]
+        beta = (0.0, 1.0 / 9, 0.5, 1.0)[(case // 2) % 4]
+        cy, cx = torch.rand(A, generator=g) * 500, torch.rand(A, generator=g) * 700
+        hh, ww = torch.rand(A, generator=g) * 100 + 8, torch.rand(A, generator=g) * 100 + 8
+        boxes = torch.stack([cy - hh / 2, cx - ww / 2, cy + hh / 2, cx + ww / 2], 1)
+        j = case % A          # the positive anchor
+        c = (case // A) % K   # its GT class
+        src = boxes[j]
+        gtb = src + torch.randn(4, generator=g) * 3
+        gtb[2:] = torch.maximum(gtb[2:], gtb[:2] + 2)
+        pred = torch.randn(4, generator=g) * 0.3
+        onehot = torch.arange(A) == j
+        losses, grads = {}, {}
+
+        d = torch.randn(1, A, 4, generator=g) * 0.3
+        d[0, j] = pred
+        d = t(d).requires_grad_(True)
+        _, loc = ops.rpn_loss(t(torch.zeros(1, A)), d, t(boxes), t(gtb.reshape(1, 1, 4)),
+                              t(torch.zeros(1, A, dtype=torch.int64)), t(onehot[None]),
+                              t(onehot[None]), weights, beta, scale=1.0)
+        loc.backward()
+        losses["rpn"], grads["rpn"] = loc.detach(), d.grad[0, j]
+
+        for nreg in (1, K):
+            col = 0 if nreg == 1 else c
+            d = torch.randn(1, nreg * 4, generator=g) * 0.3
+            d[0, col * 4:col * 4 + 4] = pred
+            d = t(d).requires_grad_(True)
+            _, box = ops.fast_rcnn_loss(t(torch.zeros(1, K + 1)), d, t(src[None]),
+                                        t(torch.tensor([c])), t(gtb[None]),
+                                        t(torch.tensor([True])), weights, beta)
+            box.backward()
+            losses[f"frcn{nreg}"] = box.detach()
+            grads[f"frcn{nreg}"] = d.grad[0, col * 4:col * 4 + 4]
+
+        d = torch.randn(1, 1, 1, A * 4, generator=g) * 0.3
+        d[0, 0, 0, j * 4:j * 4 + 4] = pred
+        d = t(d).requires_grad_(True)
+        labels = torch.where(onehot, 1, -1)[None]
+        _, box = ops.retina_loss([t(torch.zeros(1, 1, 1, A * K))], [d], t(boxes),
+                                 t(gtb.reshape(1, 1, 4)), t(torch.tensor([[c]])),
+                                 t(torch.zeros(1, A, dtype=torch.int64)), t(labels), K, A, 0.25,
+                                 2.0, beta, weights)
+        box.backward()
+        losses["retina"], grads["retina"] = box.detach(), d.grad[0, 0, 0, j * 4:j * 4 + 4]
+
+        for name in ("frcn1", f"frcn{K}", "retina"):
+            where = (case, name, weights, beta, src.tolist(), gtb.tolist(), pred.tolist())
+            assert torch.equal(losses[name], losses["rpn"]), (where, losses)
+            assert torch.equal(grads[name], grads["rpn"]), (where, grads)
+        assert losses["rpn"] > 0 and grads["rpn"].any()
+
+
 @pytest.mark.parametrize("C", [80, 1])
 def test_fused_mask_loss_matches_tensor_formulation(dev, C):
     """ops.mask_loss (csrc/roi_losses.hip) == mask_rcnn_loss's tensor
