@@ -19,7 +19,7 @@ def _fused_ok(x):
 
 
 def _fused(x, code, alpha=0.0):
-    from . import ops  # (ops imports nothing from here; kept local to the GPU path)
+    from . import ops  # (activation_ is ops/detect.py's; the package imports nothing from here)
     return ops.activation_(x if x.is_contiguous() else x.contiguous(), code, alpha)
 
 

@@ -102,13 +102,13 @@ def _wgrad(x, gy, w_shape, stride, pb, pe, want_bias=False, accumulate_into=None
     no bias gradient: the caller adds its column sum).
 
     Routed by measurement (tools/bench_kernels.py --only wgrad, MI355X):
-    with split products (the default, ops.CONV_MATH) every KxK and every 1x1
+    with split products (the default, ops.conv.CONV_MATH) every KxK and every 1x1
     over >= 8k output pixels runs on the MFMA wgrad kernel (bias gradient
     fused; FPN p2 3x3 154 TF/s vs MIOpen's 122, mask-head 3x3 147 vs 110);
     smaller 1x1 -> X^T . dY as one hipBLASLt GEMM.  With f32 products the
     KxK go to MIOpen's igemm wrw, which beats the f32 MFMA kernel there."""
     KH, KW, Cin, Cout = w_shape
-    split = ops.CONV_MATH == "split"
+    split = ops.conv.CONV_MATH == "split"
     eligible = Cin % 4 == 0 and Cout % 4 == 0
     acc_w, acc_b = accumulate_into if accumulate_into is not None else (None, None)
 

@@ -26,6 +26,10 @@ from ..postprocessing import detector_postprocess
 from ..roi_heads import build_roi_heads
 from .build import META_ARCH_REGISTRY
 
+# Device images preprocessed by d2mi_preprocess_images (False: torch's
+# subtract / divide / flip / pad, five launches; tests compare).
+FUSED_PREPROCESS = True
+
 
 class _Preprocess:
     def _init_preprocess(self, cfg):
@@ -39,7 +43,7 @@ class _Preprocess:
     def preprocess_image(self, batched_inputs):
         from ...layers import ops
         x = batched_inputs["image"]
-        if x.is_cuda and ops.FUSED_PREPROCESS and x.dim() == 4 and x.shape[-1] == 3:
+        if x.is_cuda and FUSED_PREPROCESS and x.dim() == 4 and x.shape[-1] == 3:
             # one launch: normalise, flip, pad (d2mi_preprocess_images)
             images = ops.preprocess_images(x, self.pixel_mean, self.pixel_std,
                                            self.input_format == "BGR", self.neck.size_divisibility)
@@ -75,7 +79,7 @@ class GeneralizedRCNN(_Preprocess, Layer):
         backward (box + mask poolers), which always consumes the hand-off."""
         from ...layers import handoff, ops
         rh, pg = self.roi_heads, self.proposal_generator
-        if (pg is None or not getattr(rh, "mask_on", False) or not ops.MERGED_BWD
+        if (pg is None or not getattr(rh, "mask_on", False) or not ops.roi.MERGED_BWD
                 or not hasattr(pg, "rpn_head")):
             return
         shared = set(rh.in_features) & set(getattr(pg, "in_features", ()))

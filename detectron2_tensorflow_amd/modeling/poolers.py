@@ -54,7 +54,7 @@ class ROIPooler(Layer):
     def pool(self, x, boxes, box_img, return_levels=False, grad_share=None):
         """x: list of NHWC maps; boxes [R, 4] image px; box_img [R] image index.
         grad_share: a handoff.PoolerShare shared with another pooling of the same maps whose
-        backward also runs (ops._RoIAlignFn): one gradient map set, no add."""
+        backward also runs (ops.roi._RoIAlignFn): one gradient map set, no add."""
         assert len(x) == len(self.scales), (
             f"unequal value, num_level_assignments={len(self.scales)}, but x is list of {len(x)} Tensors")
         return ops.roi_align(x, boxes, box_img, self.output_size, self.scales, self.sampling_ratio,

@@ -52,6 +52,9 @@ ROI_HEADS_REGISTRY = Registry("ROI_HEADS")
 # GPU: the sampled ROI batch in fg-first order straight from the fused
 # sampler (d2mi_subsample order output) instead of a key sort (A/B switch)
 FUSED_ORDER = True
+# The label / take / mask-prep glue on d2mi_roi_gt_classes and
+# d2mi_roi_sample_take (False: torch's gathers, selects, argsort; tests compare).
+FUSED_SAMPLE_TAKE = True
 
 
 def build_roi_heads(cfg, input_shape, **kwargs):
@@ -102,7 +105,7 @@ class ROIHeads(Layer):
                                       crowd=crowd, difficult=difficult)
         K = self.num_classes
         S = self.batch_size_per_image
-        if boxes.is_cuda and FUSED_ORDER and ops.FUSED_SAMPLE_TAKE:
+        if boxes.is_cuda and FUSED_ORDER and FUSED_SAMPLE_TAKE:
             # two launches for the glue (d2mi_roi_gt_classes, d2mi_roi_sample_take),
             # the mask branch's fg-first inputs and foreground count included
             gt_classes = ops.roi_gt_classes(labels, matches, targets["gt_classes"], pvalid, K)
@@ -219,7 +222,7 @@ class StandardROIHeads(ROIHeads):
                 raise ValueError("ROI-head training needs targets")
             sampled = self.label_and_sample_proposals(proposals, targets)
             # the box and mask poolers read the same p2..p5: one gradient map
-            # set for both backwards (ops._RoIAlignFn grad_share)
+            # set for both backwards (ops.roi._RoIAlignFn grad_share)
             share = handoff.PoolerShare() if self.mask_on else None
             # the mask branch's foreground count is read while the box branch
             # is enqueued (the device never idles at the read)

@@ -163,10 +163,11 @@ def test_former_environment_knobs_steer_the_plans_in_process(lib):
     assert ops.conv_plan(*p3, pad=(1, 1)) == before
     assert ops.wgrad_plan(*wshape, pad=(1, 1)) == wbefore
     # set_tuning drops the cached workspace sizes: they depend on the knobs
-    ops._CONV_WS["stale"] = 1
-    ops._WGRAD_WS["stale"] = 1
+    # (written and checked where conv2d_nhwc / conv2d_wgrad look them up)
+    ops.conv._CONV_WS["stale"] = 1
+    ops.conv._WGRAD_WS["stale"] = 1
     ops.set_tuning("conv_tail", 1)
-    assert not ops._CONV_WS and not ops._WGRAD_WS
+    assert not ops.conv._CONV_WS and not ops.conv._WGRAD_WS
 
 
 def test_plan_dicts_name_the_fields(lib):

@@ -1504,17 +1504,20 @@ def test_roi_align_backward_grad_share_matches_autograd_sum(dev, merged):
     (d2mi_roi_align_bwd2: one sort on (pixel, set) keys, each set's run summed
     apart, then added); else the first backward writes the maps and the second
     accumulates into them (d2mi_roi_align_bwd_ex accumulate).  Small boxes
-    pile > 64 contributions onto single pixels (the split-run path)."""
-    import detectron2_tensorflow_amd.layers.ops as O
-    O.MERGED_BWD = merged
+    pile > 64 contributions onto single pixels (the split-run path).  The arm
+    that ran is asserted from its launch records, so a toggle write that
+    reaches no reader fails."""
+    from detectron2_tensorflow_amd.layers.ops import roi
+    roi.MERGED_BWD = merged
     try:
-        _grad_share_case(dev)
+        _grad_share_case(dev, merged)
     finally:
-        O.MERGED_BWD = True
+        roi.MERGED_BWD = True
 
 
-def _grad_share_case(dev):
+def _grad_share_case(dev, merged):
     from detectron2_tensorflow_amd.layers.handoff import PoolerShare
+    from detectron2_tensorflow_amd.layers.ops import KernelTimer
     rng = np.random.default_rng(45)
     N, IH, IW, C = 2, 256, 320, 64
     strides = [4, 8, 16, 32]
@@ -1532,7 +1535,16 @@ def _grad_share_case(dev):
                              scales, 0, True, grad_share=share)
         o2 = ops().roi_align(xs, torch.from_numpy(b2).to(dev), torch.from_numpy(i2).to(dev),
                              (14, 14), scales, 0, True, grad_share=share)
-        torch.autograd.backward([o1, o2], [g1, g2])
+        saved = (KernelTimer.enabled, KernelTimer.detail, KernelTimer.records)
+        KernelTimer.reset()
+        try:
+            torch.autograd.backward([o1, o2], [g1, g2])
+            launches = [r[0] for r in KernelTimer.records].count("roi_align_bwd")
+        finally:
+            KernelTimer.enabled, KernelTimer.detail, KernelTimer.records = saved
+        # the merged arm is ONE backward over both ROI sets; the other arm, like
+        # autograd's two independent backwards, launches one per pooling
+        assert launches == (1 if share is not None and merged else 2)
         grads.append([x.grad.clone() for x in xs])
         assert share is None or share.empty  # the second backward took the maps
     for a, b in zip(*grads):
@@ -1810,16 +1822,16 @@ def test_roi_sample_take_matches_torch_glue(dev, case):
                "gt_is_crowd": torch.from_numpy(crowd).to(dev),
                "gt_difficult": torch.from_numpy(diff).to(dev),
                "gt_masks": torch.rand(N, G, 56, 56, device=dev)}
-    from detectron2_tensorflow_amd.layers import ops as lops
+    from detectron2_tensorflow_amd.modeling.roi_heads import roi_heads as rh
     try:
-        lops.FUSED_SAMPLE_TAKE = False
+        rh.FUSED_SAMPLE_TAKE = False
         torch.manual_seed(11)
         ref = heads.label_and_sample_proposals(pl, targets)
-        lops.FUSED_SAMPLE_TAKE = True
+        rh.FUSED_SAMPLE_TAKE = True
         torch.manual_seed(11)
         got = heads.label_and_sample_proposals(pl, targets)
     finally:
-        lops.FUSED_SAMPLE_TAKE = True
+        rh.FUSED_SAMPLE_TAKE = True
     fused = got.pop("_mask_prep")
     assert sorted(got) == sorted(ref)
     for k in ref:

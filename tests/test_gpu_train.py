@@ -751,7 +751,7 @@ def test_rpn_head_level_weight_grad_accumulator_is_exact(dev, monkeypatch, one_l
 
 
 def test_deferred_roi_pixel_passes_are_exact(dev, monkeypatch):
-    """ops.DEFER_PIXELS: the merged box / mask pooler backward prepares its
+    """ops.roi.DEFER_PIXELS: the merged box / mask pooler backward prepares its
     contributions once (d2mi_roi_align_bwd2_ex phase 1) and each FPN level's
     pixel pass runs inside the RPN head conv's backward, into that conv's
     full dgrad map (phase 2, accumulate) -- no map clear, no epilogue add of
@@ -777,7 +777,7 @@ def test_deferred_roi_pixel_passes_are_exact(dev, monkeypatch):
     monkeypatch.setattr(handoff, "OBSERVER", observe)
     grads = {}
     for defer in (True, False):
-        monkeypatch.setattr(ops, "DEFER_PIXELS", defer)
+        monkeypatch.setattr(ops.roi, "DEFER_PIXELS", defer)
         model.zero_grad(set_to_none=True)
         applied.clear()
         torch.manual_seed(1)

@@ -393,7 +393,7 @@ def test_pooler_share_assigns_set0_and_set1_by_arrival():
     box, mask = ("boxes0", "ind0", rnd(40), "p0"), ("boxes1", "ind1", rnd(41), "p1")
     out = []
 
-    def backward(mine):  # the merged branch of ops._RoIAlignFn.backward
+    def backward(mine):  # the merged branch of ops.roi._RoIAlignFn.backward
         first = share.rois.take()
         if first is None:
             share.rois.put(mine)

@@ -399,7 +399,7 @@ def test_cpu_training_step_restatement_runs_and_updates():
 
 
 def test_cell_anchor_host_cache_follows_values():
-    """ops._cell_host_array (the host copy of the cell anchors handed to the
+    """ops.detect._cell_host_array (the host copy of the cell anchors handed to the
     fused proposal / RetinaNet decoders) must follow the anchors' VALUES:
     models with different anchor sizes built and freed in one process (tensors
     at reused addresses), and in-place edits, never see a stale copy."""
@@ -408,14 +408,14 @@ def test_cell_anchor_host_cache_follows_values():
     for i in range(40):
         sizes = (32 * (1 + i % 3),)
         cells = [generate_cell_anchors(sizes, (0.5, 1, 2))]
-        arr, n = ops._cell_host_array(cells)
+        arr, n = ops.detect._cell_host_array(cells)
         want = torch.as_tensor(cells[0], dtype=torch.float32).reshape(-1).tolist()
         assert n == len(want) and list(arr)[:n] == want
         del cells, arr
     c = generate_cell_anchors((64,), (1,))
-    ops._cell_host_array([c])
+    ops.detect._cell_host_array([c])
     c.mul_(2)  # in place: the version counter moves, the copy is refreshed
-    arr, n = ops._cell_host_array([c])
+    arr, n = ops.detect._cell_host_array([c])
     assert list(arr)[:n] == c.reshape(-1).tolist()
 
 

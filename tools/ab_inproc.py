@@ -66,7 +66,7 @@ def _rpn_concat(on):
 
 def _defer_pixels(on):
     from detectron2_tensorflow_amd.layers import ops
-    ops.DEFER_PIXELS = on
+    ops.roi.DEFER_PIXELS = on
 
 
 def _gc_off(on):
