@@ -63,6 +63,11 @@ def _tree():
                                  (30.0, 30.0, 15.0, 15.0)),
             "IOUS": (0.5, 0.6, 0.7),
         },
+        # (RelationBoxHead; the last three are read by nothing, as in the reference)
+        "ROI_BOX_RELATION_HEAD": {
+            "NUM_GROUPS": 16, "KEY_DIM": 64, "GEOMETRY_EMBEDDING_DIM": 64,
+            "DUPLICATE_REMOVAL_IOU": 0.5, "RANK_EMBEDDING_DIM": 128, "NMS_NUM_GROUP": 16,
+        },
         "ROI_MASK_HEAD": {
             "NAME": "MaskRCNNConvUpsampleHead", "POOLER_RESOLUTION": 14,
             "POOLER_SAMPLING_RATIO": 0, "NUM_CONV": 0, "CONV_DIM": 256, "NORM": "",

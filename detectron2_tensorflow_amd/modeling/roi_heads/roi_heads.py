@@ -258,6 +258,11 @@ class StandardROIHeads(ROIHeads):
         pred = self.forward_with_given_boxes(features, pred)
         return pred, {}
 
+    def _box_features(self, x, boxes, valid):
+        """The box head on the pooled rows of boxes [N, P, 4] / valid [N, P]
+        (a subclass whose head looks at the proposals routes them here)."""
+        return self.box_head(x)
+
     def _forward_box(self, feats, proposals, image_shapes):
         boxes = proposals.boxes
         valid = proposals.get_field("is_valid")
@@ -267,7 +272,7 @@ class StandardROIHeads(ROIHeads):
         slot = _cached_index("slot", N, P, dev)
         slot = torch.where(valid.reshape(-1), slot, torch.full_like(slot, -1))
         x = self.box_pooler.pool(feats, boxes.reshape(-1, 4), img)
-        x = self.box_head(x)
+        x = self._box_features(x, boxes, valid)
         logits, deltas = self.box_predictor(x)
         ob, os_, oc, ov, _ = fast_rcnn_inference(
             logits, deltas, boxes.reshape(-1, 4), img, slot, N, P, image_shapes,
@@ -286,7 +291,7 @@ class StandardROIHeads(ROIHeads):
         img = _cached_index("img", N, S, boxes.device)
         x = self.box_pooler.pool(feats, boxes.reshape(-1, 4).contiguous(), img,
                                  grad_share=grad_share)
-        logits, deltas = self.box_predictor(self.box_head(x))
+        logits, deltas = self.box_predictor(self._box_features(x, boxes, sampled["is_valid"]))
         return fast_rcnn_losses(logits, deltas, boxes.reshape(-1, 4), sampled["gt_classes"].reshape(-1),
                                 sampled["gt_boxes"].reshape(-1, 4), sampled["is_valid"].reshape(-1),
                                 self.box2box_transform, self.smooth_l1_beta)

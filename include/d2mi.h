@@ -906,6 +906,41 @@ int d2mi_cascade_refine(const float* deltas, const float* boxes, const uint8_t* 
                         int64_t* out_gt_classes, int64_t* out_gt_index, float* out_gt_boxes,
                         uint8_t* out_loss_valid, void* stream);
 
+/* ------------------------------------------------ Relation Networks attention
+ * ObjectRelationModule.call with compute_geometry_embeddings
+ * (lib/modeling/roi_heads/relation_module.py:29-89, :141-194) on the dense
+ * [N, R] proposal layout, without any tensor of R x R extent: boxes [N, R, 4]
+ * (yxyx f32, 16-B aligned), valid uint8 [N, R], q / k [N, R, G*dk], v
+ * [N, R, dv], wg [E, G] and bg [G] (the geometry 1x1 conv).  An invalid slot
+ * takes part as SparseBoxList.to_dense leaves it: box 0, q = k = v = 0 (its
+ * rows of q / k / v are not read); the softmax runs over all R columns.
+ *   out [N, R, G*dv]: out[n, i, g*dv + d] = sum_j P[n, i, g, j] v[n, j, d],
+ *                     zero rows for invalid i (the residual is the caller's);
+ *   lse [N, R, 2, G]: the log-sum-exp of row (n, i, g)'s logits for the backward,
+ *                     in its two parts (the maximum m, then the sum l of
+ *                     exp(logit - m): lse = m + log l), so that the backward's
+ *                     exp(logit - m) / l uses the l that out was divided by.
+ * Envelope: 1 <= G <= 16, 1 <= dk <= 8, dv % 4 == 0 and dv <= 64, E % 8 == 0
+ * and E <= 128, 1 <= N <= 65535, R >= 1; anything else is refused on the host.
+ * One launch, no workspace, no host synchronisation. */
+int d2mi_relation_fwd(const float* boxes, const uint8_t* valid, const float* q, const float* k,
+                      const float* v, const float* wg, const float* bg, int N, int R, int G,
+                      int dk, int dv, int E, float* out, float* lse, void* stream);
+/* The backward of d2mi_relation_fwd (relation_module.py:29-89, :141-194
+ * differentiated; no gradient to the boxes): out / lse as the forward wrote
+ * them, d_out [N, R, G*dv] -> d_q, d_k [N, R, G*dk], d_v [N, R, dv] (zero rows
+ * for invalid slots), d_wg [E, G], d_bg [G]; d log(max(relu(x), 1e-6)) / dx
+ * is 1 / x where x > 1e-6 and 0 elsewhere.  Embedding and probabilities are
+ * recomputed from lse; sums over rows and over pairs go through fixed-order
+ * partials in the workspace (no atomics: two runs are bit-identical).  Four
+ * launches, no host synchronisation. */
+size_t d2mi_relation_workspace_size(int N, int R, int G, int dk, int dv, int E);
+int d2mi_relation_bwd(const float* boxes, const uint8_t* valid, const float* q, const float* k,
+                      const float* v, const float* wg, const float* bg, const float* out,
+                      const float* lse, const float* d_out, int N, int R, int G, int dk, int dv,
+                      int E, float* d_q, float* d_k, float* d_v, float* d_wg, float* d_bg,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------ RPN losses
  * RPNOutputs.losses (rpn_outputs.py:306-401) after matching and sampling:
  * logits [N,P], deltas [N,P,4], anchors [P,4], gt_boxes [N,G,4] (yxyx),
