@@ -651,7 +651,7 @@ size_t d2mi_conv2d_wgrad_workspace_size(int N, int H, int W, int Cin, int Cout, 
  * (operands: 8 = dw is 16-byte aligned, 32 / 64 the workspace).  16 integers:
  *   [0] kernel: 0 f32 <TM,TN>, 1 split <TM,TN>, 2 split 128x128 at three
  *       workgroups per CU, 3 warp-specialised, 4 the same with the incremental
- *       pixel cursor, 5 the same loading two chunks ahead;
+ *       pixel cursor;
  *   [1] TM  [2] TN  [3] BM  [4] BN  [5] Cin tiles  [6] Cout tiles  [7] tiles
  *   [8] 32-pixel chunks  [9] splits (grid = tiles x splits)  [10] chunks per
  *   split  [11] slabs are written (splits > 1 or accumulating)  [12] reduce

@@ -1556,7 +1556,7 @@ def test_conv_levels_matches_per_level_convs(dev, cout, relu):
     """d2mi_conv2d_nhwc_levels (one launch over RetinaNet's P3..P7 at 640x640,
     shared weights) == conv2d_nhwc per level: the same per-tile arithmetic,
     summation order differing only where a small level alone would split K;
-    and level 0 vs float64.  Cout 720 = the cls_score head (a partial N tile),
+    and every level vs float64.  Cout 720 = the cls_score head (a partial N tile),
     36 = bbox_pred (narrow: f32 MFMA)."""
     from detectron2_tensorflow_amd.layers import ops
     g = torch.Generator(device="cpu").manual_seed(11)
@@ -1573,12 +1573,13 @@ def test_conv_levels_matches_per_level_convs(dev, cout, relu):
         ref = ops.conv2d_nhwc(x, wp, b, 1, (1, 1), relu=relu)
         assert y.shape == ref.shape
         torch.testing.assert_close(y, ref, rtol=1e-5, atol=1e-5 * float(ref.abs().max()))
-    x64 = xs[0].double().permute(0, 3, 1, 2)
-    r64 = torch.nn.functional.conv2d(x64, w.double().permute(3, 2, 0, 1), b.double(), padding=1)
-    r64 = r64.permute(0, 2, 3, 1)
-    if relu:
-        r64 = r64.clamp_min(0)
-    torch.testing.assert_close(ys[0].double(), r64, rtol=1e-4, atol=1e-4)
+    w64, b64 = w.double().permute(3, 2, 0, 1), b.double()
+    for x, y in zip(xs, ys):  # every level, the small ones that share tiles' rounds included
+        r64 = torch.nn.functional.conv2d(x.double().permute(0, 3, 1, 2), w64, b64, padding=1)
+        r64 = r64.permute(0, 2, 3, 1)
+        if relu:
+            r64 = r64.clamp_min(0)
+        torch.testing.assert_close(y.double(), r64, rtol=1e-4, atol=1e-4)
 
 
 def test_pack_weights_many_and_pack_group(dev):
