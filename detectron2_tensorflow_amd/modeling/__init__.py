@@ -11,5 +11,5 @@ from .poolers import ROIPooler, assign_boxes_to_levels
 from .proposal_generator import PROPOSAL_GENERATOR_REGISTRY, RPN, RPN_HEAD_REGISTRY
 from .roi_heads import (ROI_BOX_HEAD_REGISTRY, ROI_HEADS_REGISTRY, ROI_MASK_HEAD_REGISTRY,
                         CascadeROIHeads, ObjectRelationModule, RelationBoxHead,
-                        RelationRoiHeads, StandardROIHeads)
+                        RelationRoiHeads, Res5ROIHeads, StandardROIHeads)
 from .single_stage_heads import SINGLE_STAGE_HEADS_REGISTRY, RetinaNetHead

@@ -51,7 +51,12 @@ def mask_rcnn_loss(pred_mask_logits, boxes, gt_boxes, gt_classes, gt_masks, mask
     masks = gt_masks.to(torch.float32)[..., None].contiguous()
     ind = torch.where(fg, mask_ind.to(torch.int32), 0)
     with torch.no_grad():
-        target = tf_crop_and_resize(masks, boxes.detach().contiguous(), ind, (Hm, Wm))
+        if masks.is_cuda:
+            target = tf_crop_and_resize(masks, boxes.detach().contiguous(), ind, (Hm, Wm))
+        else:  # (CPU tensors: the crop's tensor formulation, res5_dense.py)
+            from .res5_dense import crop_and_resize_dense
+            target = crop_and_resize_dense(masks, boxes.detach(), ind, (Hm, Wm),
+                                           box_mode=ops.BOX_MODE_RAW, pad=False)
         target = torch.round(target[..., 0])
     if pred_mask_logits.is_cuda and FUSED_LOSSES:
         return ops.mask_loss(pred_mask_logits, target, gt_classes, fg)

@@ -379,3 +379,227 @@ class StandardROIHeads(ROIHeads):
         masks = masks * valid[:, None, None].to(masks.dtype)
         instances.add_field("pred_masks", masks.reshape(N, D, *masks.shape[1:]))
         return instances
+
+
+@ROI_HEADS_REGISTRY.register()
+class Res5ROIHeads(StandardROIHeads):
+    """The C4 head (lib/modeling/roi_heads/roi_heads.py:261-408): one pooler on
+    res4, the res5 stage over the pooled rows, the box predictor on their
+    spatial mean and the mask head on rows of the same res5 output.
+
+    The sampling, the fg-first mask rows, the foreground-count read and the
+    MASK_ROW_BUCKET padding are StandardROIHeads'; there is one pooling and one
+    res5 per training step.  The mean and the mask rows' gather are one launch
+    (ops.res5_pool), and so is their backward.  Training is eager: the count
+    read sits inside the forward (engine.graphed refuses the head).
+
+    ELIDE_STRIDE: with STRIDE_IN_1X1, an even POOLER_RESOLUTION 2n and
+    POOLER_SAMPLING_RATIO 0, block_1's two stride-2 1x1 convs read only the
+    even grid of the 2n x 2n crop, which is itself an n x n crop of a modified
+    box (_even_grid_boxes): pool that and run block_1 at stride 1, the same
+    weights.  Any other setting pools the full crop.
+    Deviation: the reference's training branch reads an
+    undefined name and hands the mask head's tuple to the loss; the evident
+    intent, the loss on the head's mask logits, is what runs here."""
+    # On by default: ahead of the literal path in tools/res5_ab.py (1.02x at
+    # inference on 1000 proposals, 6.4x in training on 2 x 512 rows:
+    # profiles/res5_ab.json, DESIGN.md section 5 "C4 head").
+    ELIDE_STRIDE = True
+    # (the pooled map has one reader, the head: no RPN / pooler gradient pair)
+    merged_pool_backward = False
+
+    def __init__(self, cfg, input_shape, **kwargs):
+        ROIHeads.__init__(self, cfg, input_shape, **kwargs)
+        from ..backbone.resnet import BottleneckBlock, Stage, resnet_arg_scope
+        from ...layers.convolutional import FoldGroup
+        assert len(self.in_features) == 1
+        b, r = cfg.MODEL.ROI_BOX_HEAD, cfg.MODEL.RESNETS
+        res = b.POOLER_RESOLUTION
+        scales = (1.0 / self.feature_strides[self.in_features[0]],)
+        self.mask_on = cfg.MODEL.MASK_ON
+        self.pooler = ROIPooler(res, scales, b.POOLER_SAMPLING_RATIO, b.POOLER_TYPE)
+        assert not r.DEFORM_ON_PER_STAGE[-1], "Deformable conv is not yet supported in res5 head."
+        out_channels = r.RES2_OUT_CHANNELS * 8  # res5 is 8x res2
+        kw = {"in_channels": out_channels // 2, "out_channels": out_channels,
+              "bottleneck_channels": r.NUM_GROUPS * r.WIDTH_PER_GROUP * 8,
+              "num_groups": r.NUM_GROUPS, "stride_in_1x1": r.STRIDE_IN_1X1}
+        with resnet_arg_scope(False, r.NORM):
+            self.res5 = Stage(BottleneckBlock, block_kwargs=kw, num_blocks=3, first_stride=2,
+                              scope="res5")
+        FoldGroup.attach(self.res5)
+        self.out_channels = out_channels
+        # the elision's n x n pooler, where its conditions hold
+        self.half_pooler = None
+        if r.STRIDE_IN_1X1 and b.POOLER_SAMPLING_RATIO == 0 and res % 2 == 0:
+            self.half_pooler = ROIPooler(res // 2, scales, 0, b.POOLER_TYPE)
+        self.box_predictor = FastRCNNOutputLayers(out_channels, self.num_classes,
+                                                  self.cls_agnostic_bbox_reg, scope="fastrcnn")
+        self.mask_compact_rows = True
+        self.defer_mask_loss = False
+        self.last_mask_rows = None
+        if self.mask_on:
+            self.use_mini_masks = cfg.TRANSFORM.RESIZE.USE_MINI_MASKS
+            self.mask_head = build_mask_head(
+                cfg, ShapeSpec(channels=out_channels, width=res, height=res), scope="mask_head")
+
+    def elides(self):
+        return self.ELIDE_STRIDE and self.half_pooler is not None
+
+    def _even_grid_boxes(self, boxes):
+        """The boxes whose n x n crop is the even grid (2i, 2j) of ``boxes``'
+        2n x 2n crop.  ROIAlignV2 (aligned, sample i at y0 + (i + 1/2) h / 2n):
+        the same size, moved up and left by a quarter bin of the n x n crop,
+        (h / 4n, w / 4n).  ROIAlign (tf.image.crop_and_resize spacing h / (2n -
+        1) from y0): the same corner, the size scaled by (2n - 2) / (2n - 1)."""
+        n = self.half_pooler.output_size[0]
+        hw = boxes[:, 2:] - boxes[:, :2]
+        if self.pooler.aligned:
+            q = hw / (4.0 * n)
+            return torch.cat([boxes[:, :2] - q, boxes[:, 2:] - q], 1)
+        return torch.cat([boxes[:, :2], boxes[:, :2] + hw * ((2.0 * n - 2.0) / (2.0 * n - 1.0))], 1)
+
+    def _pool(self, feats, boxes, img):
+        """The res5 input of boxes [R, 4]: (rows [R, h, w, C], the stride block_1 runs at)."""
+        pooler, stride = self.pooler, None
+        if self.elides():
+            pooler, stride, boxes = self.half_pooler, 1, self._even_grid_boxes(boxes)
+        if feats[0].is_cuda:
+            return pooler.pool(feats, boxes.contiguous(), img), stride
+        from ...layers.ops import BOX_MODE_ALIGNED, BOX_MODE_UNALIGNED
+        from .res5_dense import crop_and_resize_dense
+        if pooler.sampling_ratio > 0:
+            raise NotImplementedError("the crop's tensor formulation takes one sample per bin")
+        mode = BOX_MODE_ALIGNED if pooler.aligned else BOX_MODE_UNALIGNED
+        return crop_and_resize_dense(feats[0], boxes, img, pooler.output_size, pooler.scales[0],
+                                     mode), stride
+
+    def _res5(self, x, stride=None):
+        if not x.is_cuda:
+            from .res5_dense import stage_dense
+            return stage_dense(self.res5, x, stride)
+        if stride is None:
+            return self.res5(x)
+        # block_1 at ``stride``: its strided convs read their stride at call time
+        strided = [c for c in (self.res5.blocks[0].shortcut, self.res5.blocks[0].conv1)
+                   if c is not None and c.stride > 1]
+        saved = [c.stride for c in strided]
+        try:
+            for c in strided:
+                c.stride = stride
+            return self.res5(x)
+        finally:
+            for c, s in zip(strided, saved):
+                c.stride = s
+
+    def _shared_roi_transform(self, feats, boxes, img):
+        x, stride = self._pool(feats, boxes, img)
+        return self._res5(x, stride)
+
+    def _pool_gather(self, x, dst=None, rows=0):
+        """(the spatial mean [R, C], the rows dst names [rows, h, w, C] or None)
+        of the res5 output x [R, h, w, C]."""
+        R, h, w, C = x.shape
+        fn = ops.res5_pool if x.is_cuda and ops.res5.FUSED_POOL and C % 4 == 0 \
+            else ops.res5_pool_dense
+        pooled, y = fn(x.reshape(R, h * w, C), dst, rows)
+        return pooled, (y.reshape(rows, h, w, C) if y is not None else None)
+
+    def _mask_head(self, x):
+        if x.is_cuda:
+            return self.mask_head(x)
+        from .res5_dense import mask_head_dense
+        return mask_head_dense(self.mask_head, x)
+
+    def _mask_dst(self, fg, rows, N, S):
+        """dst [N*S] int32 of the gather: mask row m < rows is the m-th slot
+        of _mask_prep's order (fg first, each group in slot order) over the
+        first F slots per image; slot k of that [N, F] layout is sampled row
+        (k // F) * S + k % F."""
+        F_ = fg.numel() // N
+        order = torch.argsort((~fg).to(torch.uint8), stable=True)[:rows]
+        src = torch.div(order, F_, rounding_mode="floor") * S + order % F_
+        dst = torch.full((N * S,), -1, dtype=torch.int32, device=fg.device)
+        dst[src] = torch.arange(rows, dtype=torch.int32, device=fg.device)
+        return dst
+
+    def call(self, images, features, proposals, targets=None):
+        feats = [features[f] for f in self.in_features]
+        if not self.training:
+            pred = self._forward_box(feats, proposals, images.image_shapes)
+            return self.forward_with_given_boxes(features, pred), {}
+        if targets is None:
+            raise ValueError("ROI-head training needs targets")
+        sampled = self.label_and_sample_proposals(proposals, targets)
+        fused = sampled.pop("_mask_prep", None)
+        pending = prep = None
+        if self.mask_on:
+            fg = fused[1] if fused is not None else self._mask_fg(sampled)
+            # the foreground count is read while the pooling and res5 are enqueued
+            pending = host_sync.start_read(fused[2] if fused is not None else fg.sum())
+            if fused is not None:
+                gm = targets["gt_masks"]
+                prep = (fused[0], gm.reshape(gm.shape[0] * gm.shape[1], *gm.shape[2:]), fg)
+            else:
+                prep = self._mask_prep(sampled, targets, fg)
+        boxes = sampled["boxes"]
+        N, S = boxes.shape[:2]
+        img = _cached_index("img", N, S, boxes.device)
+        x = self._shared_roi_transform(feats, boxes.reshape(-1, 4), img)
+        dst, rows = None, 0
+        if self.mask_on:
+            ts, gm, fg_all = prep
+            rows = self.mask_rows(host_sync.finish_read(pending)[0], fg_all.numel())
+            self.last_mask_rows = rows
+            dst = self._mask_dst(fg_all, rows, N, S)
+        pooled, mask_x = self._pool_gather(x, dst, rows)
+        logits, deltas = self.box_predictor(pooled)
+        losses = fast_rcnn_losses(logits, deltas, boxes.reshape(-1, 4),
+                                  sampled["gt_classes"].reshape(-1),
+                                  sampled["gt_boxes"].reshape(-1, 4),
+                                  sampled["is_valid"].reshape(-1), self.box2box_transform,
+                                  self.smooth_l1_beta)
+        if self.mask_on:
+            mboxes, cls, fg, _, mind, gt_boxes = (t[:rows] for t in ts)
+            _, mask_logits = self._mask_head(mask_x)
+            losses["loss_mask"] = mask_rcnn_loss(mask_logits, mboxes, gt_boxes, cls, gm, mind, fg,
+                                                 self.use_mini_masks)
+        return sampled, losses
+
+    def _forward_box(self, feats, proposals, image_shapes):
+        boxes = proposals.boxes
+        valid = proposals.get_field("is_valid")
+        N, P = valid.shape
+        dev = boxes.device
+        img = _cached_index("img", N, P, dev)
+        slot = _cached_index("slot", N, P, dev)
+        slot = torch.where(valid.reshape(-1), slot, torch.full_like(slot, -1))
+        x = self._shared_roi_transform(feats, boxes.reshape(-1, 4), img)
+        logits, deltas = self.box_predictor(self._pool_gather(x)[0])
+        ob, os_, oc, ov, _ = fast_rcnn_inference(
+            logits, deltas, boxes.reshape(-1, 4), img, slot, N, P, image_shapes,
+            self.box2box_transform, self.test_score_thresh, self.test_nms_thresh,
+            self.test_detections_per_img, self.test_nms_cls_agnostic)
+        res = BoxList(ob)
+        res.add_field("scores", os_)
+        res.add_field("pred_classes", oc)
+        res.add_field("is_valid", ov)
+        res.set_tracking("image_shape", image_shapes)
+        return res
+
+    def forward_with_given_boxes(self, features, instances, image_shape=None):
+        assert not self.training
+        assert instances.has_field("pred_classes")
+        if not self.mask_on:
+            return instances
+        feats = [features[f] for f in self.in_features]
+        boxes = instances.boxes
+        N, D = boxes.shape[:2]
+        img = _cached_index("img", N, D, boxes.device)
+        # the detections through the same pooler and res5 (_shared_roi_transform)
+        x = self._shared_roi_transform(feats, boxes.reshape(-1, 4), img)
+        _, logits = self._mask_head(x)
+        masks = mask_rcnn_inference(logits, instances.get_field("pred_classes").reshape(-1))
+        valid = instances.get_field("is_valid").reshape(-1)
+        masks = masks * valid[:, None, None].to(masks.dtype)
+        instances.add_field("pred_masks", masks.reshape(N, D, *masks.shape[1:]))
+        return instances

@@ -1229,6 +1229,28 @@ int d2mi_panoptic_combine(const uint8_t* masks, const float* scores, const int64
                           float* seg_bbox, uint8_t* seg_is_valid, float* seg_area,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------ C4 head (Res5ROIHeads)
+ * The two readers of the res5 output X [R, P, C] f32 (P = H*W) of
+ * lib/modeling/roi_heads/roi_heads.py:345-373 in one pass over X:
+ *   pooled[r, c] = (sum_p X[r, p, c]) / P    tf.reduce_mean(box_features, [1, 2])
+ *   Y[dst[r]]    = X[r] where dst[r] >= 0    tf.gather(box_features, fg_inds)
+ * The sum runs in increasing p from 0.f (one fixed order: bitwise
+ * reproducible) and is divided by (float)P.  dst [R] int32 (nullable: no
+ * gather): the row of Y [M, P, C] that takes X[r], or -1.  Precondition: the
+ * values are in [-1, M) and no two rows name the same destination; rows of Y
+ * no dst names are left unwritten.  (A value >= M is not dereferenced: the row
+ * is skipped and bit 1 of the device error word is set.)  C % 4 == 0, P >= 1;
+ * X, pooled, Y 16-byte aligned.  R == 0 is a no-op. */
+int d2mi_res5_pool_fwd(const float* X, int R, int P, int C, const int32_t* dst, int M,
+                       float* pooled, float* Y, void* stream);
+/* Gradient of the above as the one gradient of X: every element of dX
+ * [R, P, C] is written once,
+ *   dX[r, p, c] = dpooled[r, c] / P + (dst[r] >= 0 ? dY[dst[r], p, c] : 0)
+ * (no zero fill, no atomics, bitwise reproducible).  dY [M, P, C] and dst are
+ * nullable (no gather: the broadcast alone); M bounds dst as in the forward. */
+int d2mi_res5_pool_bwd(const float* dpooled, const float* dY, const int32_t* dst, int R, int P,
+                       int C, int M, float* dX, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
