@@ -7,7 +7,9 @@
 
 namespace d2mi {
 
-constexpr int kMaxA = 12;
+// Anchors per cell of an RPN / RetinaNet level: 5 sizes x 3 aspect ratios on
+// the single-level C4 and DC5 RPNs.  (yolo.hip keeps its own limit.)
+constexpr int kMaxA = 15;
 
 // Per-level geometry of a pyramid's score / delta tensors and its anchors.
 struct Levels {

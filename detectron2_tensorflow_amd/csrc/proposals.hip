@@ -147,6 +147,51 @@ __global__ __launch_bounds__(1024) void rpn_decode_compact_kernel(
   if (threadIdx.x == 0) scount[s] = run;
 }
 
+// Pre-NMS top-k above kLdsSortCap (the single-level C4 / DC5 RPNs in training:
+// PRE_NMS_TOPK_TRAIN = 12000 of a res4 grid's 63,000 anchors), which the radix
+// select's candidate buffer does not hold: a full sort of every segment
+// instead.  rpn_wide_keys_kernel writes desc_key(logit, position) of every
+// candidate, sort_keys_segmented orders them (score descending, ties to the
+// lowest position; NaN / -inf last as ~0), rpn_wide_select_kernel turns the
+// first min(k, len) of them into the top-k lists the decode kernels read.
+constexpr int kRpnWideCap = 16384;  // largest k (the NMS mask is k * k bits per segment)
+
+__global__ void rpn_wide_keys_kernel(const float* __restrict__ base,
+                                     const int64_t* __restrict__ seg_start,
+                                     const int32_t* __restrict__ seg_len, int cap,
+                                     uint64_t* __restrict__ keys) {
+  const int s = blockIdx.y;
+  const int len = min(seg_len[s], cap);
+  const float* src = base + seg_start[s];
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < len; i += gridDim.x * blockDim.x)
+    keys[(size_t)s * cap + i] = desc_key(src[i], (uint32_t)i);
+}
+
+// tvals / tidx [S, k] and tcount [S] as topk_core_ex leaves them, except that
+// the never-selected scores (NaN, -inf: sorted last) are not counted -- the
+// decode kernels drop those themselves.  The score is read back from the
+// logits (the key's word does not tell -0.0 from +0.0).
+__global__ void rpn_wide_select_kernel(const float* __restrict__ base,
+                                       const int64_t* __restrict__ seg_start,
+                                       const int32_t* __restrict__ seg_len,
+                                       const uint64_t* __restrict__ sorted, int cap, int k,
+                                       float* __restrict__ tvals, int32_t* __restrict__ tidx,
+                                       int32_t* __restrict__ tcount) {
+  const int s = blockIdx.y;
+  const int kk = min(k, min(seg_len[s], cap));
+  const float* src = base + seg_start[s];
+  const uint64_t* sk = sorted + (size_t)s * cap;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && (kk == 0 || sk[0] == ~0ull)) tcount[s] = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < kk; i += gridDim.x * blockDim.x) {
+    const uint64_t key = sk[i];
+    if (key == ~0ull) continue;
+    const uint32_t q = (uint32_t)(key & 0xffffffffu);  // < len: written by rpn_wide_keys_kernel
+    tvals[(size_t)s * k + i] = src[q];
+    tidx[(size_t)s * k + i] = (int32_t)q;
+    if (i + 1 == kk || sk[i + 1] == ~0ull) tcount[s] = i + 1;  // the last selectable one
+  }
+}
+
 // One workgroup per image: concat the per-level NMS survivors, top_k(post,
 // sorted=True) with the concat position as tie-break, zero-pad.
 __global__ __launch_bounds__(1024) void rpn_merge_kernel(
@@ -709,8 +754,12 @@ struct RpnWs {
   int32_t* num_keep;
   void* nms_ws;
   size_t nms_bytes;
+  // k > kLdsSortCap only: every candidate's key, the sorted keys, the sort's space
+  uint64_t *wide_keys, *wide_sorted;
+  void* wide_sort_ws;
+  size_t wide_sort_bytes;
   template <typename A>
-  void lay(A& a, int N, int L, int k, int post) {
+  void lay(A& a, int N, int L, int k, int post, int maxlen) {
     const int S = N * L;
     seg_start = a.template take<int64_t>(S);
     seg_len = a.template take<int32_t>(S);
@@ -726,6 +775,12 @@ struct RpnWs {
     num_keep = a.template take<int32_t>(S);
     nms_bytes = nms_core_workspace_size(S, k);
     nms_ws = a.template take<char>(nms_bytes);
+    if (k > kLdsSortCap) {
+      wide_keys = a.template take<uint64_t>((size_t)S * maxlen);
+      wide_sorted = a.template take<uint64_t>((size_t)S * maxlen);
+      wide_sort_bytes = sort_workspace_size(S, maxlen);
+      wide_sort_ws = a.template take<char>(wide_sort_bytes);
+    }
   }
 };
 }  // namespace
@@ -735,7 +790,7 @@ extern "C" size_t d2mi_rpn_proposals_workspace_size(int N, int L, const int32_t*
   int maxlen = 0;
   for (int l = 0; l < L; ++l) maxlen = std::max(maxlen, level_hw[2 * l] * level_hw[2 * l + 1] * A);
   const int k = std::max(1, std::min(pre_nms_topk, maxlen));
-  return layout_bytes<RpnWs>(N, L, k, post_nms_topk);
+  return layout_bytes<RpnWs>(N, L, k, post_nms_topk, maxlen);
 }
 
 extern "C" int d2mi_rpn_proposals(const float* const* logits, const float* const* deltas,
@@ -788,18 +843,31 @@ extern "C" int d2mi_rpn_proposals_ex(const float* const* logits, const float* co
   int maxlen = 0;
   for (int l = 0; l < L; ++l) maxlen = std::max(maxlen, lv.H[l] * lv.W[l] * A);
   const int k = std::max(1, std::min(pre_nms_topk, maxlen));
-  D2MI_REQUIRE(k <= kLdsSortCap, "pre_nms_topk=%d exceeds %d", k, kLdsSortCap);
+  D2MI_REQUIRE(k <= kRpnWideCap, "pre_nms_topk=%d exceeds %d", k, kRpnWideCap);
   const int S = N * L;
   Workspace w(workspace, workspace_bytes);
   RpnWs o;
-  o.lay(w, N, L, k, post_nms_topk);
+  o.lay(w, N, L, k, post_nms_topk, maxlen);
   D2MI_REQUIRE(w.ok(), "RPN workspace too small (%zu < %zu)", workspace_bytes, w.off);
   hipLaunchKernelGGL(seg_setup_kernel, dim3((S + 63) / 64), dim3(64), 0, st, lv, N, 1, k,
                      o.seg_start, o.seg_len, (int32_t*)nullptr);
   D2MI_LAUNCH_CHECK();
-  rc = topk_core_ex(logits[0], o.seg_start, o.seg_len, nullptr, S, maxlen, k, 0, o.tvals, o.tidx,
-                    o.tcount, o.topk_ws, o.topk_bytes, st);
-  if (rc) return rc;
+  if (k <= kLdsSortCap) {
+    rc = topk_core_ex(logits[0], o.seg_start, o.seg_len, nullptr, S, maxlen, k, 0, o.tvals,
+                      o.tidx, o.tcount, o.topk_ws, o.topk_bytes, st);
+    if (rc) return rc;
+  } else {  // the wide route: sort every segment, keep its first k
+    hipLaunchKernelGGL(rpn_wide_keys_kernel, dim3(grid1(maxlen, 256, 256), S), dim3(256), 0, st,
+                       logits[0], o.seg_start, o.seg_len, maxlen, o.wide_keys);
+    D2MI_LAUNCH_CHECK();
+    rc = sort_keys_segmented(o.wide_keys, o.wide_sorted, o.seg_len, S, maxlen, o.wide_sort_ws,
+                             o.wide_sort_bytes, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(rpn_wide_select_kernel, dim3(grid1(k, 256, 64), S), dim3(256), 0, st,
+                       logits[0], o.seg_start, o.seg_len, o.wide_sorted, maxlen, k, o.tvals,
+                       o.tidx, o.tcount);
+    D2MI_LAUNCH_CHECK();
+  }
   if (tuning(kTuneRpnCompact) != 0) {
     // nms_core's own layout of the NMS workspace (its sort keys unused)
     Workspace nw(o.nms_ws, o.nms_bytes);

@@ -10,6 +10,14 @@
 // pixel for Cin = 256), the chunk's G rows staged in LDS and broadcast, 16
 // f32 accumulators per thread; per-chunk partials then reduced in chunk
 // order by a second kernel (deterministic, no atomics).
+//
+// Wider outputs (the 15-anchor head of the single-level C4 / DC5 RPNs: Cout =
+// 75 -> 76): the same pass per block of 16 output columns, the column blocks a
+// second grid dimension.  A workgroup stages only its 16 columns of G, writes
+// those columns of the chunk partial [chunks][Cin + 1][Cout] and owns their
+// bias entries; the X chunk is read once per column block (5 times at Cout =
+// 76).  Cout <= 16 is one column block; every width has the same partial
+// layout and reduce, so a column's sum does not depend on the width.
 #include <algorithm>
 
 #include "common.h"
@@ -19,7 +27,8 @@ namespace d2mi {
 namespace {
 
 constexpr int kChunk = 128;    // pixels per workgroup
-constexpr int kMaxCout = 16;
+constexpr int kMaxCout = 16;       // output columns per workgroup (one column block)
+constexpr int kMaxCoutWide = 80;   // widest gradient: five column blocks
 
 __global__ __launch_bounds__(256) void wgrad_skinny_partial_kernel(
     const float* __restrict__ x, const float* __restrict__ g, int P, int Cin, int Cout,
@@ -28,14 +37,16 @@ __global__ __launch_bounds__(256) void wgrad_skinny_partial_kernel(
   const int chunk = blockIdx.x;
   const int p0 = chunk * kChunk;
   const int np = min(kChunk, P - p0);
+  const int j0 = blockIdx.y * kMaxCout;    // this workgroup's column block
+  const int nc = min(kMaxCout, Cout - j0);
   // LDS rows padded to kMaxCout (zeros): compile-time strides, so the
   // broadcast reads below are 16-B LDS loads
   for (int i = threadIdx.x; i < kChunk * kMaxCout; i += blockDim.x) {
     const int p = i / kMaxCout, j = i - p * kMaxCout;
-    gs[i] = (p < np && j < Cout) ? g[(size_t)(p0 + p) * Cout + j] : 0.f;
+    gs[i] = (p < np && j < nc) ? g[(size_t)(p0 + p) * Cout + j0 + j] : 0.f;
   }
   __syncthreads();
-  float* out = partial + (size_t)chunk * (Cin + 1) * Cout;
+  float* out = partial + (size_t)chunk * (Cin + 1) * Cout + j0;
   for (int c = threadIdx.x; c < Cin; c += blockDim.x) {
     float acc[kMaxCout];
 #pragma unroll
@@ -58,9 +69,9 @@ __global__ __launch_bounds__(256) void wgrad_skinny_partial_kernel(
     }
 #pragma unroll
     for (int j = 0; j < kMaxCout; ++j)
-      if (j < Cout) out[(size_t)c * Cout + j] = acc[j];
+      if (j < nc) out[(size_t)c * Cout + j] = acc[j];
   }
-  if (threadIdx.x < Cout) {  // bias row: column sums of the chunk's G
+  if (threadIdx.x < nc) {  // bias row: column sums of the chunk's G
     float s = 0.f;
     for (int p = 0; p < np; ++p) s += gs[p * kMaxCout + threadIdx.x];
     out[(size_t)Cin * Cout + threadIdx.x] = s;
@@ -72,95 +83,97 @@ __global__ __launch_bounds__(256) void wgrad_skinny_partial_kernel(
 // 1 KiB float4 wave load for Cin = 256, four rows in flight per wave: 4x the
 // bytes per load of the scalar form, which left this pass latency-bound),
 // and the waves' sums are combined in wave order through LDS before the
-// chunk partial is written.  kChunk4 pixels per workgroup.
+// chunk partial is written.  kChunk4 pixels per workgroup.  j0: the first of
+// the workgroup's (at most 16) output columns; cb: the first of its (at most
+// 256) input channels -- a pass of 256 channels is a workgroup of its own (the
+// third grid dimension; one pass for the FPN head's Cin = 256), so the one
+// level of a C4 / DC5 head (66 chunks at 2 x 50 x 84) still fills the GPU.
 constexpr int kChunk4 = 128;
 
 __device__ __forceinline__ void skinny_partial4(const float* __restrict__ x,
                                                 const float* __restrict__ g, int P, int Cin,
-                                                int Cout, int chunk,
+                                                int Cout, int chunk, int j0, int cb,
                                                 float* __restrict__ partial, float4* lds) {
   float* gs = reinterpret_cast<float*>(lds);
   const int p0 = chunk * kChunk4;
   const int np = min(kChunk4, P - p0);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  float* out = partial + (size_t)chunk * (Cin + 1) * Cout;
-  for (int cb = 0; cb < Cin; cb += 256) {  // 256 input channels per pass
-    __syncthreads();
-    for (int i = threadIdx.x; i < kChunk4 * kMaxCout; i += blockDim.x) {
-      const int p = i / kMaxCout, j = i - p * kMaxCout;
-      gs[i] = (p < np && j < Cout) ? g[(size_t)(p0 + p) * Cout + j] : 0.f;
-    }
-    __syncthreads();
-    const int c = cb + 4 * lane;
-    const bool live = c < Cin;
-    float4 acc[kMaxCout];
+  const int nc = min(kMaxCout, Cout - j0);
+  float* out = partial + (size_t)chunk * (Cin + 1) * Cout + j0;
+  for (int i = threadIdx.x; i < kChunk4 * kMaxCout; i += blockDim.x) {
+    const int p = i / kMaxCout, j = i - p * kMaxCout;
+    gs[i] = (p < np && j < nc) ? g[(size_t)(p0 + p) * Cout + j0 + j] : 0.f;
+  }
+  __syncthreads();
+  const int c = cb + 4 * lane;
+  const bool live = c < Cin;
+  float4 acc[kMaxCout];
 #pragma unroll
-    for (int j = 0; j < kMaxCout; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (live) {
-      const float* xp = x + (size_t)p0 * Cin + c;
-      int p = wv;
-      for (; p + 12 < np; p += 16) {  // 4 rows in flight per wave
-        float4 xv[4];
+  for (int j = 0; j < kMaxCout; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (live) {
+    const float* xp = x + (size_t)p0 * Cin + c;
+    int p = wv;
+    for (; p + 12 < np; p += 16) {  // 4 rows in flight per wave
+      float4 xv[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) xv[u] = *reinterpret_cast<const float4*>(xp + (size_t)(p + 4 * u) * Cin);
+      for (int u = 0; u < 4; ++u) xv[u] = *reinterpret_cast<const float4*>(xp + (size_t)(p + 4 * u) * Cin);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const float* gr = gs + (p + 4 * u) * kMaxCout;
-#pragma unroll
-          for (int j = 0; j < kMaxCout; ++j) {
-            const float gv = gr[j];
-            acc[j].x = fmaf(xv[u].x, gv, acc[j].x);
-            acc[j].y = fmaf(xv[u].y, gv, acc[j].y);
-            acc[j].z = fmaf(xv[u].z, gv, acc[j].z);
-            acc[j].w = fmaf(xv[u].w, gv, acc[j].w);
-          }
-        }
-      }
-      for (; p < np; p += 4) {
-        const float4 xv = *reinterpret_cast<const float4*>(xp + (size_t)p * Cin);
-        const float* gr = gs + p * kMaxCout;
+      for (int u = 0; u < 4; ++u) {
+        const float* gr = gs + (p + 4 * u) * kMaxCout;
 #pragma unroll
         for (int j = 0; j < kMaxCout; ++j) {
           const float gv = gr[j];
-          acc[j].x = fmaf(xv.x, gv, acc[j].x);
-          acc[j].y = fmaf(xv.y, gv, acc[j].y);
-          acc[j].z = fmaf(xv.z, gv, acc[j].z);
-          acc[j].w = fmaf(xv.w, gv, acc[j].w);
+          acc[j].x = fmaf(xv[u].x, gv, acc[j].x);
+          acc[j].y = fmaf(xv[u].y, gv, acc[j].y);
+          acc[j].z = fmaf(xv[u].z, gv, acc[j].z);
+          acc[j].w = fmaf(xv[u].w, gv, acc[j].w);
         }
       }
     }
-    // bias row of this chunk (once): column sums of G in pixel order
-    float bsum = 0.f;
-    if (cb == 0 && threadIdx.x < Cout)
-      for (int q = 0; q < np; ++q) bsum += gs[q * kMaxCout + threadIdx.x];
-    __syncthreads();  // gs no longer read: the region takes the wave sums
-    if (wv > 0) {
-#pragma unroll
-      for (int j = 0; j < kMaxCout; ++j) lds[((wv - 1) * 64 + lane) * kMaxCout + j] = acc[j];
-    }
-    __syncthreads();
-    if (wv == 0 && live) {
-      // ((w0 + w1) + w2) + w3 per output, one output column at a time
+    for (; p < np; p += 4) {
+      const float4 xv = *reinterpret_cast<const float4*>(xp + (size_t)p * Cin);
+      const float* gr = gs + p * kMaxCout;
 #pragma unroll
       for (int j = 0; j < kMaxCout; ++j) {
-        float4 t = acc[j];
-        for (int w = 0; w < 3; ++w) {
-          const float4 v = lds[(w * 64 + lane) * kMaxCout + j];
-          t.x += v.x;
-          t.y += v.y;
-          t.z += v.z;
-          t.w += v.w;
-        }
-        if (j < Cout) {
-          out[(size_t)c * Cout + j] = t.x;
-          out[(size_t)(c + 1) * Cout + j] = t.y;
-          out[(size_t)(c + 2) * Cout + j] = t.z;
-          out[(size_t)(c + 3) * Cout + j] = t.w;
-        }
+        const float gv = gr[j];
+        acc[j].x = fmaf(xv.x, gv, acc[j].x);
+        acc[j].y = fmaf(xv.y, gv, acc[j].y);
+        acc[j].z = fmaf(xv.z, gv, acc[j].z);
+        acc[j].w = fmaf(xv.w, gv, acc[j].w);
       }
     }
-    if (cb == 0 && threadIdx.x < Cout) out[(size_t)Cin * Cout + threadIdx.x] = bsum;
   }
+  // bias row of this chunk (once): column sums of G in pixel order
+  float bsum = 0.f;
+  if (cb == 0 && threadIdx.x < nc)
+    for (int q = 0; q < np; ++q) bsum += gs[q * kMaxCout + threadIdx.x];
+  __syncthreads();  // gs no longer read: the region takes the wave sums
+  if (wv > 0) {
+#pragma unroll
+    for (int j = 0; j < kMaxCout; ++j) lds[((wv - 1) * 64 + lane) * kMaxCout + j] = acc[j];
+  }
+  __syncthreads();
+  if (wv == 0 && live) {
+    // ((w0 + w1) + w2) + w3 per output, one output column at a time
+#pragma unroll
+    for (int j = 0; j < kMaxCout; ++j) {
+      float4 t = acc[j];
+      for (int w = 0; w < 3; ++w) {
+        const float4 v = lds[(w * 64 + lane) * kMaxCout + j];
+        t.x += v.x;
+        t.y += v.y;
+        t.z += v.z;
+        t.w += v.w;
+      }
+      if (j < nc) {
+        out[(size_t)c * Cout + j] = t.x;
+        out[(size_t)(c + 1) * Cout + j] = t.y;
+        out[(size_t)(c + 2) * Cout + j] = t.z;
+        out[(size_t)(c + 3) * Cout + j] = t.w;
+      }
+    }
+  }
+  if (cb == 0 && threadIdx.x < nc) out[(size_t)Cin * Cout + threadIdx.x] = bsum;
 }
 
 __global__ __launch_bounds__(256, 2) void wgrad_skinny_partial4_kernel(
@@ -169,7 +182,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_skinny_partial4_kernel(
   // the chunk's G rows (16 KiB); reused for the wave combine (3 x 64 lanes x
   // 64 floats = 48 KiB)
   __shared__ float4 lds[3 * 64 * 16];
-  skinny_partial4(x, g, P, Cin, Cout, blockIdx.x, partial, lds);
+  skinny_partial4(x, g, P, Cin, Cout, blockIdx.x, blockIdx.y * kMaxCout, blockIdx.z * 256, partial,
+                  lds);
 }
 
 // Several calls' (levels') passes in one launch: the levels' chunks one
@@ -190,6 +204,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_skinny_partial4_levels_kernel(
   int l = 0;
   while (l + 1 < lv.L && (int)blockIdx.x >= lv.cb[l + 1]) ++l;
   skinny_partial4(lv.x[l], lv.g[l], lv.P[l], Cin, Cout, blockIdx.x - lv.cb[l],
+                  blockIdx.y * kMaxCout, blockIdx.z * 256,
                   partial + (size_t)lv.cb[l] * (Cin + 1) * Cout, lds);
 }
 
@@ -333,8 +348,9 @@ extern "C" int d2mi_wgrad_skinny(const float* x, const float* g, int P, int Cin,
 extern "C" int d2mi_wgrad_skinny_ex(const float* x, const float* g, int P, int Cin, int Cout,
                                     float* gw, float* gb, int accumulate, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-  D2MI_REQUIRE(P > 0 && Cin > 0 && Cout > 0 && Cout <= kMaxCout,
-               "wgrad_skinny: P=%d Cin=%d Cout=%d (Cout must be 1..%d)", P, Cin, Cout, kMaxCout);
+  D2MI_REQUIRE(P > 0 && Cin > 0 && Cout > 0 && Cout <= kMaxCoutWide,
+               "wgrad_skinny: P=%d Cin=%d Cout=%d (Cout must be 1..%d)", P, Cin, Cout,
+               kMaxCoutWide);
   const size_t need = d2mi_wgrad_skinny_workspace_size(P, Cin, Cout);
   D2MI_REQUIRE(workspace && workspace_bytes >= need, "wgrad_skinny workspace too small: %zu < %zu",
                workspace_bytes, need);
@@ -342,12 +358,13 @@ extern "C" int d2mi_wgrad_skinny_ex(const float* x, const float* g, int P, int C
   const int chunks = v4 ? (P + kChunk4 - 1) / kChunk4 : (P + kChunk - 1) / kChunk;
   hipStream_t st = as_stream(stream);
   float* partial = static_cast<float*>(workspace);
+  const int ncb = (Cout + kMaxCout - 1) / kMaxCout;  // column blocks
   if (v4)
-    hipLaunchKernelGGL(wgrad_skinny_partial4_kernel, dim3(chunks), dim3(256), 0, st, x, g, P, Cin,
-                       Cout, partial);
+    hipLaunchKernelGGL(wgrad_skinny_partial4_kernel, dim3(chunks, ncb, (Cin + 255) / 256),
+                       dim3(256), 0, st, x, g, P, Cin, Cout, partial);
   else
-    hipLaunchKernelGGL(wgrad_skinny_partial_kernel, dim3(chunks), dim3(256), 0, st, x, g, P, Cin,
-                       Cout, partial);
+    hipLaunchKernelGGL(wgrad_skinny_partial_kernel, dim3(chunks, ncb), dim3(256), 0, st, x, g, P,
+                       Cin, Cout, partial);
   D2MI_LAUNCH_CHECK();
   const int n = (Cin + 1) * Cout;
   hipLaunchKernelGGL(wgrad_skinny_reduce_kernel, dim3((n + kRedOut - 1) / kRedOut), dim3(256), 0,
@@ -369,9 +386,9 @@ extern "C" int d2mi_wgrad_skinny_levels(const float* const* x, const float* cons
                                         void* stream) {
   D2MI_REQUIRE(x && g && P && L > 0 && L <= kSkinnyMaxLevels,
                "wgrad_skinny_levels: 1..%d levels", kSkinnyMaxLevels);
-  D2MI_REQUIRE(Cin > 0 && Cin % 4 == 0 && Cout > 0 && Cout <= kMaxCout,
+  D2MI_REQUIRE(Cin > 0 && Cin % 4 == 0 && Cout > 0 && Cout <= kMaxCoutWide,
                "wgrad_skinny_levels: Cin=%d (a multiple of 4) Cout=%d (1..%d)", Cin, Cout,
-               kMaxCout);
+               kMaxCoutWide);
   SkinnyLevels lv = {};
   lv.L = L;
   lv.cb[0] = 0;
@@ -388,8 +405,9 @@ extern "C" int d2mi_wgrad_skinny_levels(const float* const* x, const float* cons
                "wgrad_skinny_levels workspace too small: %zu < %zu", workspace_bytes, need);
   hipStream_t st = as_stream(stream);
   float* partial = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(wgrad_skinny_partial4_levels_kernel, dim3(lv.cb[L]), dim3(256), 0, st, lv,
-                     Cin, Cout, partial);
+  hipLaunchKernelGGL(wgrad_skinny_partial4_levels_kernel,
+                     dim3(lv.cb[L], (Cout + kMaxCout - 1) / kMaxCout, (Cin + 255) / 256), dim3(256),
+                     0, st, lv, Cin, Cout, partial);
   D2MI_LAUNCH_CHECK();
   const int n = (Cin + 1) * Cout;
   hipLaunchKernelGGL(wgrad_skinny_reduce_levels_kernel, dim3((n + kRedOut - 1) / kRedOut),

@@ -37,13 +37,14 @@ namespace {
 constexpr int kYB = 256;    // predictions per score / compact workgroup
 constexpr int kNmsWG = 1024;
 constexpr int kTile = 64;
+constexpr int kYoloMaxA = 12;  // anchors per cell of a YOLO level (YoloGeo's cell tables)
 
 struct YoloGeo {
   const float* ptr[D2MI_MAX_LEVELS];  // level l: [N, H, W, A * (5 + K)]
   int32_t H[D2MI_MAX_LEVELS], W[D2MI_MAX_LEVELS];
   int32_t p0[D2MI_MAX_LEVELS + 1];    // per-image prefix of predictions (H W A)
   float stride[D2MI_MAX_LEVELS];
-  float cell_h[D2MI_MAX_LEVELS][kMaxA], cell_w[D2MI_MAX_LEVELS][kMaxA];
+  float cell_h[D2MI_MAX_LEVELS][kYoloMaxA], cell_w[D2MI_MAX_LEVELS][kYoloMaxA];
   float s[D2MI_MAX_LEVELS], half[D2MI_MAX_LEVELS];  // scale_yx, 0.5 * (scale_yx - 1)
   int32_t L, A, K, N, P;
   int32_t nb;                         // score blocks per image
@@ -339,7 +340,7 @@ struct YoloWs {
 int64_t yolo_total(int N, int L, const int32_t* level_hw, int A) {
   D2MI_REQUIRE(N >= 1, "N=%d out of range", N);
   D2MI_REQUIRE(L >= 1 && L <= D2MI_MAX_LEVELS, "L=%d out of range [1,%d]", L, D2MI_MAX_LEVELS);
-  D2MI_REQUIRE(A >= 1 && A <= kMaxA, "A=%d out of range [1,%d]", A, kMaxA);
+  D2MI_REQUIRE(A >= 1 && A <= kYoloMaxA, "A=%d out of range [1,%d]", A, kYoloMaxA);
   D2MI_REQUIRE(level_hw != nullptr, "level_hw is null");
   int64_t P = 0;
   for (int l = 0; l < L; ++l) {

@@ -536,7 +536,9 @@ def stride_scatter(g, out_shape, stride, add=None, add2=None, gate=None):
 
 
 def wgrad_skinny(x, g, with_bias=True, accumulate_into=None):
-    """1x1-conv weight (+ bias) gradient for Cout <= 16 over all pixels:
+    """1x1-conv weight (+ bias) gradient for Cout <= 80 over all pixels (one
+    streaming pass over x per 16 output columns: one for the 3-anchor RPN head's
+    16, five for the 15-anchor head's 76):
     x [..., Cin], g [..., Cout] -> (gw [1, 1, Cin, Cout] HWIO, gb [Cout] or None).
     accumulate_into: a (gw, gb) pair of an earlier call to add this one into
     (old + new, in place; returned)."""
@@ -570,7 +572,7 @@ def wgrad_skinny_levels(xs, gs, with_bias=True):
     """wgrad_skinny of several calls sharing one weight, summed in list order
     (d2mi_wgrad_skinny_levels: one partial launch + one reduce; bit-identical
     to the calls one by one with accumulate_into after the first).  xs[l]
-    [..., Cin] 16-B aligned with Cin % 4 == 0, gs[l] [..., Cout]."""
+    [..., Cin] 16-B aligned with Cin % 4 == 0, gs[l] [..., Cout], Cout <= 80."""
     xs = [_f32c(x) for x in xs]
     gs = [_f32c(g) for g in gs]
     _C.require_device(*xs, *gs)

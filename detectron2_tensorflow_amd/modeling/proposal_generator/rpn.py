@@ -40,7 +40,8 @@ class StandardRPNHead(Layer):
     # True: the head hands a handoff.RowBound from the loss to its backwards.
     # When RPN.losses declares the sampled anchors per image on it, the levels
     # where that leaves most pixel rows without a gradient run a row census
-    # of the 16-wide gradient; the shared 3x3's weight gradient then walks only
+    # of the fused 1x1's gradient (16 wide for 3 anchors); the shared 3x3's
+    # weight gradient then walks only
     # the non-zero 32-pixel chunks and its data gradient computes only the rows
     # whose window holds a non-zero row (both bit-identical to the dense
     # launches).  False: dense (A/B, tests)
@@ -66,8 +67,10 @@ class StandardRPNHead(Layer):
 
     def _fused_1x1(self):
         """The objectness (A) and anchor-delta (4A) 1x1 convs as ONE conv of
-        A + 4A outputs, zero-padded to a multiple of 4 (15 -> 16): weights
-        HWIO [1, 1, C, 16], their MFMA packing, and the bias [16]."""
+        A + 4A outputs, zero-padded to a multiple of 4 (3 anchors: 15 -> 16;
+        the single-level C4 / DC5 RPNs' 15 anchors: 75 -> 76): weights HWIO
+        [1, 1, C, 16 | 76], their MFMA packing, and the bias (w16 / b16 are
+        named for the FPN width)."""
         wo, wd = self.objectness_logits.weights, self.anchor_deltas.weights
         bo, bd = self.objectness_logits.bias, self.anchor_deltas.bias
         key = (wo._version, wd._version, bo._version, bd._version, wo.data_ptr(), wd.data_ptr())
@@ -89,7 +92,7 @@ class StandardRPNHead(Layer):
         rpn_features, logits, deltas = [], [], []
         fuse = features[0].is_cuda
         if fuse and not torch.is_grad_enabled() and len(features) <= 6:
-            # inference: the shared 3x3 and the fused 16-wide 1x1 each as ONE
+            # inference: the shared 3x3 and the fused (16- or 76-wide) 1x1 each as ONE
             # multi-level launch over p2..p6
             shares = self.conv.call_levels(list(features))
             w16, wp, b16 = self._fused_1x1()
@@ -164,10 +167,11 @@ class _LevelViews(list):
 
 
 class _RPNGatherFn(torch.autograd.Function):
-    """The fused 1x1's per-level [N, H, W, 16] outputs -> (objectness logits
+    """The fused 1x1's per-level [N, H, W, C] outputs (C = 16 for 3 anchors,
+    76 for 15) -> (objectness logits
     [N, T*A], anchor deltas [N, T*A, 4]) in the level-major per-image layout
     of RPNOutputs (rpn_outputs.py:346-357), by d2mi_rpn_head_gather; backward
-    = d2mi_rpn_head_scatter straight into the per-level 16-wide gradients
+    = d2mi_rpn_head_scatter straight into the per-level C-wide gradients
     (padding channel zero): no slice copies, concatenations or zero-fills."""
 
     @staticmethod
@@ -185,11 +189,13 @@ class _RPNGatherFn(torch.autograd.Function):
 
 
 class _RPNHead1x1Fn(torch.autograd.Function):
-    """Both RPN-head 1x1 convs (rpn.py:83-96) as one 16-wide conv on the MFMA
-    kernel.  Backward: the two output gradients are concatenated (+ the zero
-    pad column) into one [.., 16] gradient; the input gradient is ONE dgrad
-    conv (instead of a dgrad per head + their sum), the weight and bias
-    gradients one skinny X^T G pass (d2mi_wgrad_skinny) sliced per head.  The
+    """Both RPN-head 1x1 convs (rpn.py:83-96) as one conv of 5A outputs padded
+    to a multiple of 4 (16 wide for 3 anchors, 76 for the C4 / DC5 RPNs' 15) on
+    the MFMA kernel.  Backward: the two output gradients are concatenated (+
+    the zero pad column) into one [.., 16 | 76] gradient; the input gradient is
+    ONE dgrad conv (instead of a dgrad per head + their sum), the weight and
+    bias gradients one skinny X^T G pass (d2mi_wgrad_skinny: one sweep of x per
+    16 output columns, at most 80 columns) sliced per head.  The
     input gradient leaves through the dgrad's ReLU gate (share > 0) when share
     is a fused-ReLU conv output, which then skips its threshold_backward (the
     sole-consumer protocol of layers/convolutional.py:_ConvMFMAFn)."""
@@ -213,7 +219,7 @@ class _RPNHead1x1Fn(torch.autograd.Function):
         ctx.dims = (A, D, y.shape[-1])
         ctx.wacc = wacc
         ctx.rows = rows  # (handoff.RowBound, level) or None
-        return y  # [.., 16]: A logits, 4A deltas, zero padding (_RPNGatherFn splits it)
+        return y  # [.., 16 | 76]: A logits, 4A deltas, zero padding (_RPNGatherFn splits it)
 
     @staticmethod
     def backward(ctx, g16):
@@ -224,7 +230,8 @@ class _RPNHead1x1Fn(torch.autograd.Function):
         if ctx.rows is not None:
             # a zero g16 row is a zero row of the gradient below (the 1x1
             # dgrad maps row to row, the gate only zeroes more): census it
-            # here, 16 wide, for the shared 3x3's backward -- only under a
+            # here, at the fused width, for the shared 3x3's backward -- only
+            # under a
             # bound the loss declared, never inferred from the values
             bound, level = ctx.rows
             N, H, W = g16.shape[:3]

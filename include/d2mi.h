@@ -266,7 +266,9 @@ int d2mi_subsample(const int64_t* labels, int N, int P, long long bg_label, int 
 
 /* -------------------------------------------------------- anchors/deltas
  * DefaultAnchorGenerator.grid_anchors for one level (anchor_generator.py:92-109):
- * out[(h*W + w)*A + a] = cell[a] + (h*stride, w*stride, h*stride, w*stride). */
+ * out[(h*W + w)*A + a] = cell[a] + (h*stride, w*stride, h*stride, w*stride).
+ * 1 <= A <= 15 (5 sizes x 3 aspect ratios: the single-level C4 / DC5 RPNs);
+ * the same bound holds for d2mi_rpn_proposals[_ex] and the RetinaNet entries. */
 int d2mi_grid_anchors(int H, int W, float stride, const float* cell_anchors_host, int A,
                       float* out, void* stream);
 
@@ -285,6 +287,12 @@ int d2mi_apply_deltas(const float* deltas, const float* boxes, int N, int K,
  * level_hw   host int32 [L][2]; strides host float [L]; cell_anchors host [L][A][4]
  * image_hw   device int32 [N,2] (true image height, width)
  * out_boxes  device [N, post, 4]; out_scores [N, post]; out_valid uint8 [N, post]
+ * 1 <= A <= 15.  k = min(pre_nms_topk, max_l H_l W_l A) <= 16384.  k <= 8192
+ * runs the radix select (d2mi_topk's); above it (the single-level C4 / DC5
+ * RPNs in training: 12000 of up to 63,000 anchors) every (image, level)
+ * segment is sorted whole -- keys, the tiled and merged segmented sort, the
+ * first k kept -- with the same order: score descending, ties to the lowest
+ * index, NaN and -inf never selected.  The workspace query covers both.
  */
 size_t d2mi_rpn_proposals_workspace_size(int N, int L, const int32_t* level_hw, int A,
                                          int pre_nms_topk, int post_nms_topk);
@@ -812,11 +820,13 @@ int d2mi_paste_masks(const float* box_masks, const float* boxes, const float* yx
 
 /* ------------------------------------------------ skinny 1x1 weight gradient
  * gw[Cin][Cout] = X^T G and gb[Cout] = column sums of G over P pixels, for
- * Cout <= 16 (the RPN head's objectness + anchor-delta 1x1 convs, fused:
+ * Cout <= 80 (the RPN head's objectness + anchor-delta 1x1 convs, fused:
  * lib/modeling/proposal_generator/rpn.py:83-96, whose TF gradient is
- * Conv2DBackpropFilter + BiasAddGrad).  x [P, Cin], g [P, Cout] f32
- * contiguous; gb nullable.  Fixed-order reduction (deterministic); workspace
- * from d2mi_wgrad_skinny_workspace_size. */
+ * Conv2DBackpropFilter + BiasAddGrad; 16 outputs for 3 anchors, 76 for the
+ * C4 / DC5 RPNs' 15).  x [P, Cin], g [P, Cout] f32 contiguous; gb nullable.
+ * One streaming pass over x per block of 16 output columns (Cout <= 16: one
+ * pass).  Fixed-order reduction (deterministic); workspace from
+ * d2mi_wgrad_skinny_workspace_size: ceil(P / 128) * (Cin + 1) * Cout floats. */
 size_t d2mi_wgrad_skinny_workspace_size(int P, int Cin, int Cout);
 int d2mi_wgrad_skinny(const float* x, const float* g, int P, int Cin, int Cout, float* gw,
                       float* gb, void* workspace, size_t workspace_bytes, void* stream);
@@ -833,7 +843,9 @@ int d2mi_wgrad_skinny_ex(const float* x, const float* g, int P, int Cin, int Cou
  * g[l] [P[l], Cout]; each level summed exactly as one d2mi_wgrad_skinny call
  * and the levels added in array order (accumulate != 0: after the old gw /
  * gb) -- bit-identical to the per-level calls with accumulate after the
- * first.  workspace >= d2mi_wgrad_skinny_levels_workspace_size. */
+ * first.  Cout <= 80 as above.  workspace >=
+ * d2mi_wgrad_skinny_levels_workspace_size: (sum_l ceil(P[l] / 128)) *
+ * (Cin + 1) * Cout floats. */
 size_t d2mi_wgrad_skinny_levels_workspace_size(const int* P, int L, int Cin, int Cout);
 int d2mi_wgrad_skinny_levels(const float* const* x, const float* const* g, const int* P, int L,
                              int Cin, int Cout, float* gw, float* gb, int accumulate,
