@@ -146,6 +146,14 @@ class GraphedTrainer(Trainer):
             raise NotImplementedError(
                 "GraphedTrainer cannot capture a model with Res5ROIHeads (the C4 configs): the "
                 "head reads the foreground count inside its forward; train it with Trainer")
+        if any(getattr(m, "batch_stats", False) for m in model.modules()):
+            # the cross-replica exchange of a SyncBN cannot sit in a capture,
+            # and the captured step's memset-free and hand-off invariants have
+            # not been checked with these layers
+            raise NotImplementedError(
+                "GraphedTrainer cannot capture a model with a BatchNorm on batch statistics "
+                "(NORM \"BN\" / \"SyncBN\" in training): the SyncBN collective cannot be "
+                "captured; train it with Trainer")
         # >= 1: the first eager step makes the per-shape caches, workspaces and
         # the optimizer / fold tables, none of which may be created in a capture
         self.warmup = max(1, int(warmup))

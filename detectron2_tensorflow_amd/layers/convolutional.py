@@ -29,6 +29,12 @@ from .base import Layer
 from .normalization import BatchNorm
 
 
+def _foldable_bn(norm):
+    """A BatchNorm in the inference form: folded into the conv weights.  One on
+    batch statistics (BatchNorm.batch_stats) runs after the raw conv instead."""
+    return isinstance(norm, BatchNorm) and not norm.batch_stats
+
+
 def fix_padding(inputs, kernel_size, padding="SAME", rate=1):
     """Explicit symmetric 'SAME' padding (convolutional.py:12-23): NHWC zero pad."""
     if padding == "SAME" and kernel_size != 1:
@@ -298,7 +304,7 @@ class FoldGroup:
     @classmethod
     def attach(cls, module):
         layers = [m for m in module.modules()
-                  if isinstance(m, Conv2D) and isinstance(m.normalizer_fn, BatchNorm)]
+                  if isinstance(m, Conv2D) and _foldable_bn(m.normalizer_fn)]
         return cls(layers) if layers else None
 
     def fetch(self, layer):
@@ -313,7 +319,8 @@ class FoldGroup:
         return out
 
     def _fold(self):
-        members = [m for m in self.layers if m.weights.is_cuda and m.fold_trainable()]
+        members = [m for m in self.layers if m.weights.is_cuda and m.fold_trainable()
+                   and _foldable_bn(m.normalizer_fn)]
         entries = []
         for m in members:
             n = m.normalizer_fn
@@ -338,7 +345,7 @@ class PackGroup:
     @classmethod
     def attach(cls, module):
         layers = [m for m in module.modules()
-                  if isinstance(m, Conv2D) and not isinstance(m.normalizer_fn, BatchNorm)]
+                  if isinstance(m, Conv2D) and not _foldable_bn(m.normalizer_fn)]
         if not layers:
             return None
         g = cls()
@@ -406,6 +413,9 @@ class Conv2D(Layer):
             p = dict(self.normalizer_params or {})
             p["channels"] = self.out_channels
             self.normalizer_fn = self.normalizer(**p)
+        # a plain attribute: the one check of every call (no module lookup)
+        object.__setattr__(self, "_bn_batch_stats",
+                           bool(getattr(self.normalizer_fn, "batch_stats", False)))
         self.act_fn = get_activation(self.activation)
         self._packed = None
         self._packed_key = None
@@ -427,7 +437,7 @@ class Conv2D(Layer):
         # the normalizer's buffers)
         if kt is None or kt[0] is not w or kt[2] != w.data_ptr():
             rest = [self.bias] if self.bias is not None else []
-            if isinstance(self.normalizer_fn, BatchNorm):
+            if _foldable_bn(self.normalizer_fn):
                 n = self.normalizer_fn
                 rest += [t for t in (n.gamma, n.beta, n.moving_mean, n.moving_variance)
                          if t is not None]
@@ -445,9 +455,10 @@ class Conv2D(Layer):
         """(weights HWIO, bias, normalizer still to apply, packed-or-None) with a
         frozen BatchNorm folded in by one fused HIP kernel (d2mi_fold_frozen_bn,
         differentiable w.r.t. weights / bias / gamma / beta).  Cached while
-        autograd is off (inference)."""
+        autograd is off (inference).  A BatchNorm on batch statistics is not
+        folded: it is the normalizer still to apply."""
         norm = self.normalizer_fn
-        if not isinstance(norm, BatchNorm):
+        if not _foldable_bn(norm):
             return self.weights, self.bias, norm, None
         if not self.weights.is_cuda:
             raise RuntimeError(f"{self.scope}: the FrozenBN fold runs on the GPU (HIP)")
@@ -473,7 +484,7 @@ class Conv2D(Layer):
         norm = self.normalizer_fn
         if self.weights.requires_grad or (self.bias is not None and self.bias.requires_grad):
             return True
-        if isinstance(norm, BatchNorm):
+        if _foldable_bn(norm):
             return any(t is not None and t.requires_grad for t in (norm.gamma, norm.beta))
         return False
 
@@ -548,9 +559,13 @@ class Conv2D(Layer):
         pair_grad / join (a handoff.Pair), wacc (a handoff.LevelAccumulator),
         rows ((handoff.RowBound, level) of the output's gradient): the gradient
         hand-offs of layers/handoff.py."""
-        impl = self.impl
-        if impl == "auto":
-            impl = "mfma" if self._mfma_eligible(inputs) else "torch"
+        if self._bn_batch_stats:
+            if res_grad_to is not None or grad_from is not None:
+                raise ValueError(f"{self.scope}: res_grad_to / grad_from cannot be honoured under "
+                                 "a BatchNorm on batch statistics (the conv runs without gradient "
+                                 "hand-offs: the Slot's gradient would be lost)")
+            return self._call_batch_stats(inputs, topdown, residual, relu_after_add, final_relu, raw)
+        impl = self._pick_impl(inputs)
         w, b, norm, packed = self.effective_params(want_packed=(impl == "mfma"))
         if final_relu:
             if self.act_fn is not None:
@@ -558,27 +573,16 @@ class Conv2D(Layer):
             if impl == "torch":
                 return torch.relu_(self.call(inputs, topdown, residual))
         if impl == "mfma":
-            if not self._mfma_eligible(inputs, padded=True):
-                raise ValueError(f"{self.scope}: shape/device not supported by the MFMA conv "
-                                 f"(groups={self.num_groups}, rate={self.rate}, "
-                                 f"Cin={self.in_channels}, device={inputs.device})")
-            pads = same_pads(self.kernel_size, self.rate) if self.padding == "SAME" else (0, 0)
             fuse_relu = norm is None and (is_relu(self.act_fn) or final_relu)
             relu_after_add = relu_after_add or final_relu
             if (topdown is not None or residual is not None) and fuse_relu and not relu_after_add:
                 raise ValueError("relu(conv) + add cannot be fused; use relu_after_add")
-            padc = (-self.in_channels) % 4
             if join is not None:
-                if padc or not torch.is_grad_enabled():
+                if self.in_channels % 4 or not torch.is_grad_enabled():
                     join = None  # (a padded input is another tensor: no join)
                 else:
                     join.join_lateral()  # the pair members now leave their sum to this layer
-            if padc:
-                inputs = F.pad(inputs, (0, padc))
-                w = F.pad(w, (0, 0, 0, padc))
-                packed = None
-            if packed is None:
-                packed = self.packed_weights(w)
+            inputs, w, packed, pads = self._mfma_operands(inputs, w, packed)
             links = handoff.Links(bool(relu_input_sole_consumer), res_grad_to, grad_from,
                                   pair_grad, join, wacc, rows)
             ret = _ConvMFMAFn.apply(inputs, w, b, packed, self.stride, pads,
@@ -595,20 +599,8 @@ class Conv2D(Layer):
             if final_relu and not fuse_relu:
                 ret = torch.relu(ret)
             return ret
-        # torch (channels_last) path: backbone 3x3 convs / the stem.  A symmetric
-        # SAME pad is the conv's own zero padding (no padded copy of the input).
-        pad = 0
-        x = inputs
-        if self.padding == "SAME" and self.kernel_size != 1:
-            pb, pe = same_pads(self.kernel_size, self.rate)
-            if pb == pe:
-                pad = pb
-            else:
-                x = fix_padding(inputs, self.kernel_size, self.padding, self.rate)
-        y = F.conv2d(x.permute(0, 3, 1, 2),
-                     w.permute(3, 2, 0, 1).contiguous(memory_format=torch.channels_last), b,
-                     stride=self.stride, padding=pad, dilation=self.rate, groups=self.num_groups)
-        ret = y.permute(0, 2, 3, 1)
+        # torch (channels_last) path: backbone 3x3 convs / the stem
+        ret = self._conv_torch(inputs, w, b)
         if norm is not None:
             ret = norm(ret)
         has_add = topdown is not None or residual is not None
@@ -622,6 +614,83 @@ class Conv2D(Layer):
         if self.act_fn is not None and has_add and relu_after_add:
             ret = torch.relu_(ret) if is_relu(self.act_fn) else self.act_fn(ret)
         return ret
+
+    def _pick_impl(self, inputs):
+        impl = self.impl
+        if impl == "auto":
+            impl = "mfma" if self._mfma_eligible(inputs) else "torch"
+        return impl
+
+    def _mfma_operands(self, inputs, w, packed):
+        """(inputs, w, packed, pads) as the MFMA conv takes them: refused when
+        the shape / device is not eligible; Cin % 4 != 0 runs with zero
+        channels appended to the input and the weights (and packs those)."""
+        if not self._mfma_eligible(inputs, padded=True):
+            raise ValueError(f"{self.scope}: shape/device not supported by the MFMA conv "
+                             f"(groups={self.num_groups}, rate={self.rate}, "
+                             f"Cin={self.in_channels}, device={inputs.device})")
+        pads = same_pads(self.kernel_size, self.rate) if self.padding == "SAME" else (0, 0)
+        padc = (-self.in_channels) % 4
+        if padc:
+            inputs = F.pad(inputs, (0, padc))
+            w = F.pad(w, (0, 0, 0, padc))
+            packed = None
+        if packed is None:
+            packed = self.packed_weights(w)
+        return inputs, w, packed, pads
+
+    def _conv_torch(self, inputs, w, b):
+        """conv (+ bias) on stock PyTorch-ROCm conv2d in channels_last, as an
+        NHWC view.  A symmetric SAME pad is the conv's own zero padding (no
+        padded copy of the input)."""
+        pad = 0
+        x = inputs
+        if self.padding == "SAME" and self.kernel_size != 1:
+            pb, pe = same_pads(self.kernel_size, self.rate)
+            if pb == pe:
+                pad = pb
+            else:
+                x = fix_padding(inputs, self.kernel_size, self.padding, self.rate)
+        y = F.conv2d(x.permute(0, 3, 1, 2),
+                     w.permute(3, 2, 0, 1).contiguous(memory_format=torch.channels_last), b,
+                     stride=self.stride, padding=pad, dilation=self.rate, groups=self.num_groups)
+        return y.permute(0, 2, 3, 1)
+
+    def _conv_only(self, inputs):
+        """The conv (+ bias) alone, nothing fused and no gradient hand-off
+        (empty handoff.Links): what runs under a BatchNorm on batch
+        statistics, whose moments need the conv's raw output."""
+        w, b = self.weights, self.bias
+        if self._pick_impl(inputs) == "torch":
+            return self._conv_torch(inputs, w, b)
+        inputs, w, packed, pads = self._mfma_operands(inputs, w, None)
+        return _conv_mfma(inputs, w, b, packed, self.stride, pads, False, links=handoff.Links())
+
+    def _bn_epilogue(self, y, residual, relu_after_add, final_relu):
+        """act(bn(y)) with the adds of ``call``: the BatchNorm on batch
+        statistics takes the residual add and a ReLU into its apply pass
+        (bn + residual inside the conv would feed the sum to the moments);
+        any other activation stays the separate pass it is."""
+        if final_relu and self.act_fn is not None:
+            raise ValueError("final_relu is for layers without an activation")
+        norm = self.normalizer_fn
+        if self.act_fn is None or is_relu(self.act_fn):
+            return norm(y, relu=self.act_fn is not None or final_relu, residual=residual,
+                        relu_after_add=relu_after_add or final_relu)
+        ret = norm(y)
+        if residual is not None and relu_after_add:
+            return self.act_fn(ret + residual)
+        ret = self.act_fn(ret)
+        return ret if residual is None else ret + residual
+
+    def _call_batch_stats(self, inputs, topdown, residual, relu_after_add, final_relu, raw):
+        if topdown is not None:
+            raise ValueError(f"{self.scope}: the fused top-down add cannot precede a BatchNorm on "
+                             "batch statistics (FPN adds it after the lateral's norm)")
+        y = self._conv_only(inputs)
+        if raw:
+            return y
+        return self._bn_epilogue(y.contiguous(), residual, relu_after_add, final_relu)
 
 
 @add_arg_scope
@@ -734,6 +803,12 @@ class DeformConv2D(Conv2D):
                 self._cols_packed = ops.pack_conv_weights(w1.detach())
                 self._cols_packed_key = key
             packed = self._cols_packed
+        if self._bn_batch_stats:
+            if res_grad_to is not None:
+                raise ValueError(f"{self.scope}: res_grad_to cannot be honoured under a BatchNorm "
+                                 "on batch statistics (no gradient hand-offs there)")
+            y = _conv_mfma(cols, w1, b, packed, 1, (0, 0), False, links=handoff.Links())
+            return y if raw else self._bn_epilogue(y, residual, False, final_relu)
         fuse_relu = norm is None and (is_relu(self.act_fn) or final_relu)
         links = handoff.Links(res_grad_to=res_grad_to) if res_grad_to is not None else None
         ret = _conv_mfma(cols, w1, b, packed, 1, (0, 0), fuse_relu, residual=residual,

@@ -1,15 +1,26 @@
 """BatchNorm / GroupNorm / get_norm (lib/layers/normalization.py:15-274).
 
-The hot-path configs use FrozenBN in the backbone (MODEL.RESNETS.NORM) and no
-norm in FPN / heads.  BatchNorm here implements the inference form (moving
-statistics, which is what FrozenBN and training=False use):
-    y = x * gamma * rsqrt(var + eps) + (beta - mean * gamma * rsqrt(var + eps)).
-Training-mode batch statistics and SyncBN (broken in the reference,
-normalization.py:121-168) are not part of the hot path.
+BatchNorm has two forms, chosen when the layer is built and never read from
+torch's ``.training`` flag (``model.train()`` must not thaw a frozen layer):
+
+* the inference form (FrozenBN, ``training=False``, and every layer built
+  with no ``training`` keyword): the moving statistics,
+      y = x * gamma * rsqrt(var + eps) + (beta - mean * gamma * rsqrt(var + eps)),
+  which Conv2D folds into its weights (the hot-path configs: FrozenBN in the
+  backbone, no norm in FPN / heads);
+* the batch-statistics form (``training=True``; normalization.py:97-119):
+  the biased moments of the batch, the moving averages updated in place with
+  ``decay``, on the kernels of csrc/batch_norm.hip (ops.batch_norm_train).
+  With ``sync=True`` and more than one rank the moments are those of all
+  replicas' rows (what the reference's SyncBN branch, :120-165, means; it
+  cannot run there).
 """
+from contextlib import contextmanager
+
 import torch
 
-from ..utils.arg_scope import add_arg_scope
+from ..utils import training as _training
+from ..utils.arg_scope import add_arg_scope, arg_scope
 from . import ops
 from .base import Layer
 
@@ -17,14 +28,26 @@ from .base import Layer
 @add_arg_scope
 class BatchNorm(Layer):
     def __init__(self, channels, momentum=0.997, epsilon=1e-5, center=True, scale=True,
-                 trainable=True, sync=False, **kwargs):
-        kwargs.pop("training", None)
+                 trainable=True, sync=False, decay=0.9, **kwargs):
+        # the form is the keyword's alone: a layer built without it stays in
+        # the inference form whatever the global phase says
+        batch_stats = bool(kwargs.pop("training", False))
+        if batch_stats and not trainable:
+            raise ValueError("[BatchNorm] Frozen BatchNorm should not update EMA!")
         super().__init__(channels=channels, momentum=momentum, epsilon=epsilon, center=center,
-                         scale_=scale, trainable=trainable, sync=sync, training=False, **kwargs)
+                         scale_=scale, trainable=trainable, sync=sync, decay=decay,
+                         training=batch_stats, **kwargs)
+        object.__setattr__(self, "_batch_stats", batch_stats)
         self.beta = torch.nn.Parameter(torch.zeros(channels), requires_grad=trainable) if center else None
         self.gamma = torch.nn.Parameter(torch.ones(channels), requires_grad=trainable) if scale else None
         self.register_buffer("moving_mean", torch.zeros(channels))
         self.register_buffer("moving_variance", torch.ones(channels))
+
+    @property
+    def batch_stats(self):
+        """True: normalises with the batch's own statistics and updates the
+        moving averages; False: the inference form (foldable)."""
+        return self._batch_stats
 
     def folded(self):
         """(scale, shift) of the frozen affine transform."""
@@ -35,9 +58,27 @@ class BatchNorm(Layer):
             shift = shift + self.beta
         return scale, shift
 
-    def call(self, x):
+    def call(self, x, relu=False, residual=None, relu_after_add=False):
+        """relu / residual / relu_after_add: the ReLU and the add that follow
+        the layer in a conv (relu(bn(x)), relu(bn(x)) + residual,
+        relu(bn(x) + residual)), fused into the batch-statistics apply pass."""
+        if self._batch_stats:
+            mode = ops.norm.RELU_NONE
+            if relu:
+                mode = (ops.norm.RELU_AFTER_ADD if relu_after_add and residual is not None
+                        else ops.norm.RELU_BEFORE_ADD)
+            return ops.batch_norm_train(x, self.gamma, self.beta, self.moving_mean,
+                                        self.moving_variance, self.epsilon, self.decay,
+                                        residual, mode, self.sync)
         scale, shift = self.folded()
-        return x * scale + shift
+        y = x * scale + shift
+        if relu and not (relu_after_add and residual is not None):
+            y = torch.relu(y)
+        if residual is not None:
+            y = y + residual
+            if relu and relu_after_add:
+                y = torch.relu(y)
+        return y
 
 
 @add_arg_scope
@@ -75,6 +116,36 @@ class GroupNorm(Layer):
         if accumulate_into is not None:
             return accumulate_into.add_(y)
         return y
+
+
+def norm_phase():
+    """The global training phase, False when unset (as Layer.__init__)."""
+    try:
+        return _training.get_training_phase()
+    except ValueError:
+        return False
+
+
+@contextmanager
+def batch_norm_arg_scope(norm, freeze=False, sync=False):
+    """The ``training`` / ``sync`` keywords of the BatchNorm layers a builder
+    makes for the config string ``norm``, passed explicitly (a BatchNorm
+    built without the keyword stays in the inference form):
+    "FrozenBN", or ``freeze``: training=False; "BN" / "SyncBN": training =
+    the phase, and sync=True for "SyncBN" where the builder asks for it
+    (``sync``: the reference sets it in the backbone scopes only,
+    lib/modeling/backbone/resnet.py:35-39).  Any other norm: nothing."""
+    if norm not in ("BN", "SyncBN", "FrozenBN"):
+        yield
+        return
+    if norm == "FrozenBN" or freeze:
+        kw = {"training": False}
+    else:
+        kw = {"training": norm_phase()}
+        if norm == "SyncBN" and sync:
+            kw["sync"] = True
+    with arg_scope([BatchNorm], **kw):
+        yield
 
 
 def get_norm(norm):

@@ -18,6 +18,7 @@ from ...layers import (BatchNorm, Conv2D, DeformConv2D, Layer, ModulatedDeformCo
 from ...layers import handoff
 from ...layers.activation import is_relu
 from ...layers import initializers as init
+from ...layers.normalization import batch_norm_arg_scope
 from ...utils.arg_scope import add_arg_scope, arg_scope
 from .build import BACKBONE_REGISTRY, Backbone
 
@@ -32,9 +33,23 @@ def resnet_arg_scope(freeze, norm):
         st.enter_context(arg_scope([DeformConv2D], use_bias=False, normalizer=normalizer,
                                    normalizer_params={"scope": "norm"}, activation="relu",
                                    weights_initializer=init.variance_scaling(2.0, mode="fan_out")))
+        # FrozenBN or a frozen stage: the inference form; BN / SyncBN that
+        # train: batch statistics in the training phase, SyncBN across replicas
+        # (lib/modeling/backbone/resnet.py:35-39)
+        st.enter_context(batch_norm_arg_scope(norm, freeze=freeze, sync=True))
         if freeze:
             st.enter_context(arg_scope([Conv2D, DeformConv2D, BatchNorm], trainable=False))
         yield
+
+
+def _plain_bottleneck(block, x):
+    """A bottleneck whose convs carry a BatchNorm on batch statistics: the
+    convs run raw and hand the ReLU / residual add to the BatchNorm, so no
+    output has the fused-ReLU tag the gradient hand-offs (Pair, Slot,
+    relu_input_sole_consumer) build on: none is declared, autograd adds."""
+    sc = block.shortcut(x) if block.shortcut is not None else x
+    h = block.conv2(block.conv1(x))
+    return block.conv3(h, residual=sc.contiguous(), final_relu=True)
 
 
 @add_arg_scope
@@ -62,6 +77,8 @@ class BottleneckBlock(Layer):
                             scope="conv3")
 
     def call(self, x):
+        if self.conv1._bn_batch_stats:
+            return _plain_bottleneck(self, x)
         # projection shortcut: it and conv1 both read x; their input gradients
         # meet in the second one's epilogue instead of an autograd add
         pair = (handoff.Pair() if self.grad_pair and self.shortcut is not None and torch.is_grad_enabled()
@@ -112,6 +129,8 @@ class DeformBottleneckBlock(Layer):
                             scope="conv3")
 
     def call(self, x):
+        if self.conv1._bn_batch_stats:
+            return _plain_bottleneck(self, x)
         # the hand-offs around the block are BottleneckBlock's.  Inside it,
         # conv1's ReLU output has TWO readers (conv2's offset conv and its
         # sampler), so conv2 is not declared its sole consumer: conv1 applies

@@ -13,6 +13,7 @@ import torch
 
 from ...layers import Conv2D, Layer, ShapeSpec, get_norm, handoff, subsample, upsample
 from ...layers import initializers as init
+from ...layers.normalization import batch_norm_arg_scope
 from ...utils.arg_scope import arg_scope
 from .build import NECK_REGISTRY
 
@@ -62,9 +63,12 @@ class FPN(Layer):
         use_bias = self.norm == ""
         normalizer = get_norm(self.norm)
         lateral, output = [], []
+        # (BN / SyncBN: batch statistics in the training phase, never sync --
+        # the reference sets sync in the backbone scopes only)
         with arg_scope([Conv2D], use_bias=use_bias, normalizer=normalizer,
                        normalizer_params={"scope": "norm"},
-                       weights_initializer=init.variance_scaling(1.0)):
+                       weights_initializer=init.variance_scaling(1.0)), \
+                batch_norm_arg_scope(self.norm):
             for idx, cin in enumerate(self.in_channels):
                 stage = int(math.log2(self.in_strides[idx]))
                 lateral.append(Conv2D(cin, self.out_channels, 1, use_bias=use_bias,

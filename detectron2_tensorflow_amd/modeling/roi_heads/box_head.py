@@ -8,6 +8,7 @@ import torch
 
 from ...layers import Conv2D, Layer, Linear, get_norm
 from ...layers import initializers as init
+from ...layers.normalization import batch_norm_arg_scope
 from ...utils.arg_scope import arg_scope
 from ...utils.registry import Registry
 
@@ -27,7 +28,8 @@ class FastRCNNConvFCHead(Layer):
                        normalizer=normalizer, normalizer_params={"channels": h.CONV_DIM, "scope": "norm"},
                        activation="relu", padding="SAME",
                        weights_initializer=init.variance_scaling(2.0, mode="fan_out",
-                                                                 distribution="untruncated_normal")):
+                                                                 distribution="untruncated_normal")), \
+                batch_norm_arg_scope(h.NORM):  # (BN / SyncBN: training = the phase, no sync)
             for k in range(h.NUM_CONV):
                 convs.append(Conv2D(in_channels=self._output_size[0], scope=f"conv{k + 1}"))
                 self._output_size = (h.CONV_DIM, self._output_size[1], self._output_size[2])

@@ -6,6 +6,7 @@ import torch
 
 from ...layers import Conv2D, ConvTranspose2D, Layer, get_norm
 from ...layers import initializers as init
+from ...layers.normalization import batch_norm_arg_scope
 from ...layers import ops
 from ...utils.arg_scope import arg_scope
 from ...utils.registry import Registry
@@ -81,7 +82,8 @@ class MaskRCNNConvUpsampleHead(Layer):
         with arg_scope([Conv2D, ConvTranspose2D],
                        weights_initializer=init.variance_scaling(2.0, mode="fan_out",
                                                                  distribution="untruncated_normal"),
-                       activation="relu"):
+                       activation="relu"), \
+                batch_norm_arg_scope(m.NORM):  # (BN / SyncBN: training = the phase, no sync)
             for k in range(m.NUM_CONV):
                 convs.append(Conv2D(input_shape.channels if k == 0 else m.CONV_DIM, m.CONV_DIM, 3,
                                     use_bias=not normalizer, normalizer=normalizer,

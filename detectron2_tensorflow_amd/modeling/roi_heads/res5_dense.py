@@ -82,6 +82,9 @@ def conv_dense(x, layer, stride=None):
     if bn is not None:
         if not hasattr(bn, "moving_variance"):
             raise NotImplementedError(f"{layer.scope}: only FrozenBN has a tensor formulation here")
+        if getattr(bn, "batch_stats", False):
+            raise NotImplementedError(f"{layer.scope}: a BatchNorm on batch statistics has no "
+                                      "tensor formulation here (only the inference form)")
         y = ((y - bn.moving_mean.to(dt)) * (bn.gamma.to(dt) / torch.sqrt(
             bn.moving_variance.to(dt) + bn.epsilon)) + bn.beta.to(dt))
     return layer.act_fn(y) if layer.act_fn is not None else y

@@ -8,9 +8,9 @@ max-class score of every prediction, the threshold, the decode of the
 survivors, class-agnostic NMS and the padding to DETECTIONS_PER_IMAGE.
 
 Training is not implemented: the reference's loss (yolov4_outputs.py:266-329)
-needs training-mode batch statistics in the neck and head (NORM "BN"; the
-BatchNorm of layers/normalization.py is the inference form), YOLOMatcher and
-a CIoU loss.
+needs training-mode batch statistics in the neck and head (NORM "BN":
+layers.BatchNorm has that form, but these builders build the inference form),
+YOLOMatcher and a CIoU loss.
 """
 import torch
 

@@ -531,6 +531,58 @@ int d2mi_group_norm_nhwc_levels(const float* const* xs, const int32_t* dims, int
                                 float* const* ys, void* workspace, size_t workspace_bytes,
                                 void* stream);
 
+/* ------------------------------------------- BatchNorm, batch statistics
+ * The training form of BatchNorm.call (lib/layers/normalization.py:97-119:
+ * tf.layers.BatchNormalization(...).apply(inputs, training=True); the SyncBN
+ * branch :121-165 is the same with the moments of all replicas) on x [M, C]
+ * f32, M = N*H*W rows of an NHWC tensor (or the rows of [R, C]).  C % 4 == 0,
+ * every tensor 16-byte aligned, M >= 1.  Deterministic: fixed-order
+ * reductions, no atomics.
+ *
+ * d2mi_bn_train_stats: one read of x.  Per row chunk and channel a
+ * (count, mean, M2) triple by Welford's update, merged in chunk order by the
+ * parallel-variance formula into triple [2C + 1] = (count, mean[C], M2[C]),
+ * M2 = sum (x - mean)^2.  Workspace from d2mi_bn_train_stats_workspace_size. */
+size_t d2mi_bn_train_stats_workspace_size(long long M, int C);
+int d2mi_bn_train_stats(const float* x, long long M, int C, float* triple, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* Merges P triples (rows of [P, 2C + 1]: one locally, one per rank under
+ * SyncBN, normalization.py:121-165) in row order, weighted by their counts:
+ * mean [C], var [C] = M2 / count (biased, as tf.layers.BatchNormalization
+ * feeds its moving average) and invstd [C] = 1 / sqrt(var + eps), and
+ *   moving = moving * decay + batch * (1 - decay)    (assign_moving_average)
+ * in place on moving_mean / moving_var [C] (both required). */
+int d2mi_bn_train_finalize(const float* triples, int P, int C, float eps, float decay,
+                           float* moving_mean, float* moving_var, float* mean, float* var,
+                           float* invstd, void* stream);
+/* y = (x - mean) * invstd * gamma + beta  (normalization.py:97-119;
+ * gamma / beta nullable: scale=False / center=False) with the ops that follow
+ * it in a conv fused (convolutional.py:251-262, blocks.py:143-186):
+ *   relu_mode 0: y = z (+ residual);  1: y = relu(z) (+ residual);
+ *   relu_mode 2: y = relu(z + residual).   residual [M, C], nullable. */
+int d2mi_bn_train_apply(const float* x, long long M, int C, const float* mean,
+                        const float* invstd, const float* gamma, const float* beta,
+                        const float* residual, int relu_mode, float* y, void* stream);
+/* Backward, first pass (the gradient of normalization.py:97-119): with dz the
+ * gradient at the BatchNorm output (dy through the fused ReLU: relu_mode 1
+ * recomputes z from x as the forward did, relu_mode 2 reads y [M, C]) and
+ * xh = (x - mean) * invstd:  sums [2C] = (sum dz [C], sum dz * xh [C]) over
+ * this call's rows (dbeta and dgamma).  Workspace from
+ * d2mi_bn_train_bwd_reduce_workspace_size. */
+size_t d2mi_bn_train_bwd_reduce_workspace_size(long long M, int C);
+int d2mi_bn_train_bwd_reduce(const float* x, const float* dy, const float* y, long long M, int C,
+                             const float* mean, const float* invstd, const float* gamma,
+                             const float* beta, int relu_mode, float* sums, void* workspace,
+                             size_t workspace_bytes, void* stream);
+/* Backward, second pass: sums [2C] as above over ALL rows the statistics were
+ * taken over (every replica's under SyncBN), total_count their number:
+ *   dx = gamma * invstd * (dz - sums[c] / total - xh * sums[C + c] / total)
+ * and dresidual [M, C] = dz (nullable: no residual). */
+int d2mi_bn_train_bwd_apply(const float* x, const float* dy, const float* y, long long M, int C,
+                            const float* mean, const float* invstd, const float* gamma,
+                            const float* beta, int relu_mode, const float* sums,
+                            float total_count, float* dx, float* dresidual, void* stream);
+
 /* --------------------------------------------------------------- conv2d
  * NHWC implicit-GEMM convolution on fp32 MFMA (v_mfma_f32_32x32x2_f32),
  * lib/layers/convolutional.py:12-23 (fix_padding: symmetric pad) and
