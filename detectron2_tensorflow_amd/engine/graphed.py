@@ -71,7 +71,7 @@ import os
 import torch
 
 from ..layers import convolutional
-from ..modeling.roi_heads.roi_heads import DeferredMaskLoss, Res5ROIHeads, StandardROIHeads
+from ..modeling.roi_heads.roi_heads import DeferredMaskLoss, ROIHeads, StandardROIHeads
 from ..utils import capture, host_sync
 from .trainer import Trainer
 
@@ -140,9 +140,9 @@ class GraphedTrainer(Trainer):
     def __init__(self, cfg, model, warmup=1, experimental=False, wgrad_side=False, **kwargs):
         """experimental: accepted for the r4 call sites (no longer needed)."""
         super().__init__(cfg, model, **kwargs)
-        if any(isinstance(m, Res5ROIHeads) for m in model.modules()):
-            # its mask rows are gathered from the shared res5 output inside the
-            # forward, after the foreground-count read: no deferred mask loss
+        if any(isinstance(m, ROIHeads) and not m.mask_loss_deferrable for m in model.modules()):
+            # (Res5ROIHeads: its mask rows are gathered from the shared res5
+            # output inside the forward, after the foreground-count read)
             raise NotImplementedError(
                 "GraphedTrainer cannot capture a model with Res5ROIHeads (the C4 configs): the "
                 "head reads the foreground count inside its forward; train it with Trainer")

@@ -81,7 +81,7 @@ class GeneralizedRCNN(_Preprocess, Layer):
         rh, pg = self.roi_heads, self.proposal_generator
         if (pg is None or not getattr(rh, "mask_on", False) or not ops.roi.MERGED_BWD
                 or not hasattr(pg, "rpn_head")
-                or not getattr(rh, "merged_pool_backward", True)):  # (the C4 head pools once)
+                or not rh.merged_pool_backward):  # (the C4 head pools once)
             return
         shared = set(rh.in_features) & set(getattr(pg, "in_features", ()))
         for f in shared:

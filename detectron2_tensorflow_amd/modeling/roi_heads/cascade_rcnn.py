@@ -7,8 +7,9 @@ one launch (ops.cascade_refine: decode, clip, validity and, in training, the
 re-match against the ground truth at IOUS[k] with its gathers).  Inference
 averages the stages' softmax scores inside the fused Fast R-CNN
 post-processing (ops.fast_rcnn_inference_stages) and decodes the last stage's
-deltas.  The mask branch, the deferred mask loss and forward_with_given_boxes
-are StandardROIHeads'.
+deltas.  The step (call), the mask branch, the deferred mask loss and
+forward_with_given_boxes are StandardROIHeads'; the stage hand-overs get the
+image shapes and the ground truth as _box_losses' arguments.
 
 Deviations from the reference: stage k matches with
 its own proposal_matchers[k] threshold (the reference builds them and then
@@ -18,11 +19,9 @@ list; training validity chains through the stages.
 """
 import torch
 
-from ...layers import ShapeSpec, ops
-from ...structures import BoxList
+from ...layers import ops
 from ..box_regression import Box2BoxTransform
 from ..matcher import Matcher
-from ..poolers import ROIPooler
 from .box_head import build_box_head
 from .fast_rcnn import FastRCNNOutputLayers, fast_rcnn_losses
 from .roi_heads import ROI_HEADS_REGISTRY, StandardROIHeads, _cached_index
@@ -39,13 +38,7 @@ class CascadeROIHeads(StandardROIHeads):
         assert 1 <= self.num_cascade_stages <= 4, "the fused score average takes 1..4 stages"
         assert b.CLS_AGNOSTIC_BBOX_REG, "CascadeROIHeads only support class-agnostic regression"
         assert ious[0] == cfg.MODEL.ROI_HEADS.IOU_THRESHOLDS[0]
-        scales = tuple(1.0 / self.feature_strides[k] for k in self.in_features)
-        chans = {self.feature_channels[f] for f in self.in_features}
-        assert len(chans) == 1, chans
-        c = chans.pop()
-        self.box_pooler = ROIPooler(b.POOLER_RESOLUTION, scales, b.POOLER_SAMPLING_RATIO,
-                                    b.POOLER_TYPE)
-        pooled = ShapeSpec(channels=c, height=b.POOLER_RESOLUTION, width=b.POOLER_RESOLUTION)
+        self.box_pooler, pooled = self._pooler(b)
         heads, predictors = [], []
         self.box2box_transform = []
         # (stage 0 is matched by ROIHeads.proposal_matcher, in label_and_sample_proposals)
@@ -61,9 +54,6 @@ class CascadeROIHeads(StandardROIHeads):
                                                       allow_low_quality_matches=False))
         self.box_head = torch.nn.ModuleList(heads)
         self.box_predictor = torch.nn.ModuleList(predictors)
-        # set by call() for the duration of one forward (the inherited call
-        # passes neither to _box_losses)
-        self._cascade_image_hw = self._cascade_targets = None
 
     def _run_stage(self, feats, boxes, img, k, grad_share=None):
         x = self.box_pooler.pool(feats, boxes.reshape(-1, 4).contiguous(), img,
@@ -74,14 +64,10 @@ class CascadeROIHeads(StandardROIHeads):
             x = ops.scale_gradient(x, 1.0 / self.num_cascade_stages)
         return self.box_predictor[k](self.box_head[k](x))
 
-    def _box_losses(self, feats, sampled, grad_share=None):
+    def _box_losses(self, feats, sampled, image_shapes, targets, grad_share=None):
         """Stage 0 on the sampled proposals, stage k > 0 on stage k - 1's
-        refined boxes re-labelled at IOUS[k] (no resampling):
-        loss_cls_stage{k} / loss_box_reg_stage{k}."""
-        targets, image_hw = self._cascade_targets, self._cascade_image_hw
-        if targets is None or image_hw is None:
-            raise RuntimeError("CascadeROIHeads._box_losses runs inside call(): the stage "
-                               "hand-overs need its image shapes and targets")
+        refined boxes re-labelled at IOUS[k] against ``targets`` (no
+        resampling): loss_cls_stage{k} / loss_box_reg_stage{k}."""
         boxes = sampled["boxes"]
         N, S = boxes.shape[:2]
         img = _cached_index("img", N, S, boxes.device)
@@ -91,7 +77,7 @@ class CascadeROIHeads(StandardROIHeads):
         for k in range(self.num_cascade_stages):
             if k > 0:
                 cur = ops.cascade_refine(
-                    deltas, cur["boxes"], cur["is_valid"], image_hw,
+                    deltas, cur["boxes"], cur["is_valid"], image_shapes,
                     self.box2box_transform[k - 1].weights,
                     self.box2box_transform[k - 1].scale_clamp, gt_boxes=targets["gt_boxes"],
                     gt_valid=targets["is_valid"], gt_classes=targets["gt_classes"],
@@ -109,24 +95,8 @@ class CascadeROIHeads(StandardROIHeads):
             losses.update({f"{name}_stage{k}": v for name, v in stage.items()})
         return losses
 
-    def call(self, images, features, proposals, targets=None):
-        # the stage hand-overs need the image shapes and the ground truth,
-        # which StandardROIHeads.call does not pass to _box_losses
-        self._cascade_image_hw = images.image_shapes
-        self._cascade_targets = targets
-        try:
-            return super().call(images, features, proposals, targets)
-        finally:
-            self._cascade_image_hw = self._cascade_targets = None
-
     def _forward_box(self, feats, proposals, image_shapes):
-        boxes = proposals.boxes
-        valid = proposals.get_field("is_valid")
-        N, P = valid.shape
-        dev = boxes.device
-        img = _cached_index("img", N, P, dev)
-        slot = _cached_index("slot", N, P, dev)
-        slot = torch.where(valid.reshape(-1), slot, torch.full_like(slot, -1))
+        boxes, valid, img, slot, N, P = self._proposal_rows(proposals)
         stage_logits = []
         for k in range(self.num_cascade_stages):
             if k > 0:
@@ -136,14 +106,9 @@ class CascadeROIHeads(StandardROIHeads):
             logits, deltas = self._run_stage(feats, boxes, img, k)
             stage_logits.append(logits)
         t = self.box2box_transform[-1]
-        ob, os_, oc, ov, _ = ops.fast_rcnn_inference_stages(
+        return self._detections(*ops.fast_rcnn_inference_stages(
             stage_logits, deltas, boxes.reshape(-1, 4), img, slot, N, P, image_shapes, t.weights,
             self.test_score_thresh, self.test_nms_thresh, self.test_detections_per_img,
             cls_agnostic=self.num_classes != 1, scale_clamp=t.scale_clamp,
-            nms_cls_agnostic=self.test_nms_cls_agnostic)
-        res = BoxList(ob)
-        res.add_field("scores", os_)
-        res.add_field("pred_classes", oc)
-        res.add_field("is_valid", ov)
-        res.set_tracking("image_shape", image_shapes)
-        return res
+            nms_cls_agnostic=self.test_nms_cls_agnostic)[:4], image_shapes)
+

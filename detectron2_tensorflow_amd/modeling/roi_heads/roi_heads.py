@@ -7,6 +7,8 @@ the box branch needs no tf.where / host round trip.  The mask branch pools
 the [N, max_det] detections the same way and zeroes invalid rows — the
 values the reference's SparseBoxList.to_dense produces.
 """
+from typing import Any, NamedTuple, Optional
+
 import torch
 
 from ...layers import ShapeSpec, handoff, ops
@@ -61,12 +63,47 @@ def build_roi_heads(cfg, input_shape, **kwargs):
     return ROI_HEADS_REGISTRY.get(cfg.MODEL.ROI_HEADS.NAME)(cfg, input_shape, **kwargs)
 
 
+class MaskPrep(NamedTuple):
+    """The training mask branch's inputs over the first F = int(S *
+    POSITIVE_FRACTION) slots per image.  The six per-row tensors (ROWS; compact
+    rows: fg first, each group in slot order) are None until _prepared."""
+    fg_slots: torch.Tensor  # [N*F] bool foreground flags, in slot order
+    boxes: Optional[torch.Tensor] = None
+    classes: Optional[torch.Tensor] = None
+    fg: Optional[torch.Tensor] = None
+    img: Optional[torch.Tensor] = None
+    gt_mask_index: Optional[torch.Tensor] = None  # row of the flattened gt_masks
+    gt_boxes: Optional[torch.Tensor] = None
+    gt_masks: Optional[torch.Tensor] = None  # [N*G, ...]
+    count: Optional[torch.Tensor] = None  # device-side foreground count (the fused sampler's)
+    pending: Any = None  # the count's host read in flight (host_sync.start_read)
+
+    ROWS = ("boxes", "classes", "fg", "img", "gt_mask_index", "gt_boxes")
+
+    def head(self, n):
+        return self._replace(**{k: getattr(self, k)[:n] for k in self.ROWS})
+
+    def device_count(self):
+        return self.count if self.count is not None else self.fg_slots.sum()
+
+
 class ROIHeads(Layer):
+    # True: in training the head's poolers take the merged ROIAlign backward and
+    # meet the RPN's gradient on the shared levels (rcnn._tag_shared_levels).
+    # False where the pooled map has one reader and no pooler pair.
+    merged_pool_backward = True
+    # True: the training forward can return its mask loss unrun (a
+    # DeferredMaskLoss), so the step can be captured into hipGraphs.  False
+    # where the forward itself needs the foreground count on the host.
+    mask_loss_deferrable = True
+
     def __init__(self, cfg, input_shape, **kwargs):
         super().__init__(**kwargs)
         h = cfg.MODEL.ROI_HEADS
         self.batch_size_per_image = h.BATCH_SIZE_PER_IMAGE
         self.positive_sample_fraction = h.POSITIVE_FRACTION
+        # the first slots per image, which hold every sampled foreground proposal
+        self.mask_slots = int(h.BATCH_SIZE_PER_IMAGE * h.POSITIVE_FRACTION)
         self.test_score_thresh = h.SCORE_THRESH_TEST
         self.test_nms_thresh = h.NMS_THRESH_TEST
         self.test_nms_cls_agnostic = h.NMS_CLS_AGNOSTIC
@@ -88,6 +125,12 @@ class ROIHeads(Layer):
         (fg class / bg = NUM_CLASSES / -1), subsample, fg-first order, pad.
         Returns a dict of [N, S] tensors: boxes, gt_classes, gt_boxes, gt_index
         (matched GT row), is_valid."""
+        return self._sample(proposals, targets)[0]
+
+    def _sample(self, proposals, targets, mask_slots=0):
+        """(label_and_sample_proposals' dict, the MaskPrep over the first
+        mask_slots slots per image that the fused sampler makes in the same
+        launch, or None: mask_slots 0, or the tensor arm)."""
         boxes = proposals.boxes
         pvalid = proposals.get_field("is_valid")
         gt_boxes = targets["gt_boxes"]
@@ -111,14 +154,13 @@ class ROIHeads(Layer):
             gt_classes = ops.roi_gt_classes(labels, matches, targets["gt_classes"], pvalid, K)
             _, _, order, valid = subsample_labels(gt_classes, S, self.positive_sample_fraction, K,
                                                   order_slots=S)
-            F_ = (int(S * self.positive_sample_fraction)
-                  if getattr(self, "mask_on", False) and getattr(self, "mask_compact_rows", False)
-                  else 0)
-            sampled, mprep = ops.roi_sample_take(order, valid, boxes, gt_classes, matches,
-                                                 gt_boxes, K, F_)
-            if mprep is not None:
-                sampled["_mask_prep"] = mprep
-            return sampled
+            sampled, fused = ops.roi_sample_take(order, valid, boxes, gt_classes, matches,
+                                                 gt_boxes, K, mask_slots)
+            if fused is not None:
+                rows, fg_slots, count = fused
+                fused = MaskPrep(fg_slots, *rows, gt_masks=targets["gt_masks"].flatten(0, 1),
+                                 count=count)
+            return sampled, fused
         gcls = torch.gather(targets["gt_classes"].long(), 1, matches)
         # label 1 -> the matched GT class, 0 -> background K, -1 -> ignored;
         # invalid proposal slots -> -1
@@ -143,7 +185,27 @@ class ROIHeads(Layer):
         gidx = take(matches)
         return {"boxes": take4(boxes), "gt_classes": take(gt_classes), "gt_index": gidx,
                 "gt_boxes": torch.gather(gt_boxes, 1, gidx[..., None].expand(-1, -1, 4)),
-                "is_valid": valid}
+                "is_valid": valid}, None
+
+    def _proposal_rows(self, proposals):
+        """The inference prologue: (boxes [N, P, 4], valid [N, P], image id and
+        slot of each of the N*P rows -- slot -1 on an invalid row, which the
+        fused post-processing drops --, N, P)."""
+        boxes = proposals.boxes
+        valid = proposals.get_field("is_valid")
+        N, P = valid.shape
+        img = _cached_index("img", N, P, boxes.device)
+        slot = _cached_index("slot", N, P, boxes.device)
+        slot = torch.where(valid.reshape(-1), slot, torch.full_like(slot, -1))
+        return boxes, valid, img, slot, N, P
+
+    def _detections(self, boxes, scores, classes, valid, image_shapes):
+        res = BoxList(boxes)
+        res.add_field("scores", scores)
+        res.add_field("pred_classes", classes)
+        res.add_field("is_valid", valid)
+        res.set_tracking("image_shape", image_shapes)
+        return res
 
 
 class DeferredMaskLoss:
@@ -153,24 +215,29 @@ class DeferredMaskLoss:
     hipGraphs (engine/graphed.py) replays the forward up to here, reads
     ``count`` once, and replays the mask branch + backward graph captured for
     that row count (``compute(rows)``, run once per distinct row count at
-    capture time).  The eager trainer never sees one (defer_mask_loss False)."""
+    capture time) on the step's MaskPrep (``plan``).  The eager trainer never
+    sees one (defer_mask_loss False)."""
 
-    def __init__(self, heads, feats, sampled, targets, share, fg, prep=None, count=None):
+    def __init__(self, heads, feats, sampled, targets, plan, share):
         self.heads, self.feats, self.sampled, self.targets = heads, feats, sampled, targets
-        self.share, self.fg, self.prep = share, fg, prep
-        self.count = fg.sum() if count is None else count
-        self.slots = fg.numel()
+        self.plan, self.share = plan, share
+        self.count = plan.device_count()
+        self.slots = plan.fg_slots.numel()
 
     def rows_for(self, nfg):
         return self.heads.mask_rows(int(nfg), self.slots)
 
     def compute(self, rows):
-        return self.heads._mask_loss(self.feats, self.sampled, self.targets, self.share, None,
-                                     self.fg, rows=rows, prep=self.prep)
+        return self.heads._mask_loss(self.feats, self.sampled, self.targets, self.plan, self.share,
+                                     rows=rows)
 
 
 @ROI_HEADS_REGISTRY.register()
 class StandardROIHeads(ROIHeads):
+    """The step every ROI head runs (``call``: inference _forward_box ->
+    forward_with_given_boxes; training _sample -> _plan_mask -> _losses).  A
+    variant overrides the pieces: its layers (_init_box_head, _init_mask_head),
+    _box_losses or the whole _losses, the middle of _forward_box, _mask_outputs."""
     MASK_ROW_BUCKET = 32
     # the mask branch's fg-first ordering and per-slot gathers issued before
     # the foreground-count read, so less host work follows it
@@ -178,27 +245,7 @@ class StandardROIHeads(ROIHeads):
 
     def __init__(self, cfg, input_shape, **kwargs):
         super().__init__(cfg, input_shape, **kwargs)
-        self._init_box_head(cfg)
-        self._init_mask_head(cfg)
-
-    def _init_box_head(self, cfg):
-        b = cfg.MODEL.ROI_BOX_HEAD
-        scales = tuple(1.0 / self.feature_strides[k] for k in self.in_features)
-        chans = {self.feature_channels[f] for f in self.in_features}
-        assert len(chans) == 1, chans
-        c = chans.pop()
-        self.box_pooler = ROIPooler(b.POOLER_RESOLUTION, scales, b.POOLER_SAMPLING_RATIO,
-                                    b.POOLER_TYPE)
-        self.box_head = build_box_head(cfg, ShapeSpec(channels=c, height=b.POOLER_RESOLUTION,
-                                                      width=b.POOLER_RESOLUTION), scope="box_head")
-        self.box_predictor = FastRCNNOutputLayers(self.box_head.output_size, self.num_classes,
-                                                  self.cls_agnostic_bbox_reg, scope="box_predictor")
-
-    def _init_mask_head(self, cfg):
         self.mask_on = cfg.MODEL.MASK_ON
-        if not self.mask_on:
-            return
-        m = cfg.MODEL.ROI_MASK_HEAD
         self.use_mini_masks = cfg.TRANSFORM.RESIZE.USE_MINI_MASKS
         # True: mask head on the foreground rows only, like the reference (one
         # host sync per step); False: fixed [N, S*POSITIVE_FRACTION] rows with
@@ -208,55 +255,78 @@ class StandardROIHeads(ROIHeads):
         # returns a DeferredMaskLoss instead of reading the foreground count
         self.defer_mask_loss = False
         self.last_mask_rows = None
+        self._init_box_head(cfg)
+        if self.mask_on:
+            self._init_mask_head(cfg)
+
+    def _pooler(self, p):
+        """(the pooler of the config node p on in_features, the shape of its rows)"""
         scales = tuple(1.0 / self.feature_strides[k] for k in self.in_features)
-        c = [self.feature_channels[f] for f in self.in_features][0]
-        self.mask_pooler = ROIPooler(m.POOLER_RESOLUTION, scales, m.POOLER_SAMPLING_RATIO,
-                                     m.POOLER_TYPE)
-        self.mask_head = build_mask_head(cfg, ShapeSpec(channels=c, width=m.POOLER_RESOLUTION,
-                                                        height=m.POOLER_RESOLUTION), scope="mask_head")
+        chans = {self.feature_channels[f] for f in self.in_features}
+        assert len(chans) == 1, chans
+        return (ROIPooler(p.POOLER_RESOLUTION, scales, p.POOLER_SAMPLING_RATIO, p.POOLER_TYPE),
+                ShapeSpec(channels=chans.pop(), height=p.POOLER_RESOLUTION,
+                          width=p.POOLER_RESOLUTION))
+
+    def _init_box_head(self, cfg):
+        self.box_pooler, pooled = self._pooler(cfg.MODEL.ROI_BOX_HEAD)
+        self.box_head = build_box_head(cfg, pooled, scope="box_head")
+        self.box_predictor = FastRCNNOutputLayers(self.box_head.output_size, self.num_classes,
+                                                  self.cls_agnostic_bbox_reg, scope="box_predictor")
+
+    def _init_mask_head(self, cfg):
+        self.mask_pooler, pooled = self._pooler(cfg.MODEL.ROI_MASK_HEAD)
+        self.mask_head = build_mask_head(cfg, pooled, scope="mask_head")
 
     def call(self, images, features, proposals, targets=None):
         feats = [features[f] for f in self.in_features]
-        if self.training:
-            if targets is None:
-                raise ValueError("ROI-head training needs targets")
-            sampled = self.label_and_sample_proposals(proposals, targets)
-            # the box and mask poolers read the same p2..p5: one gradient map
-            # set for both backwards (ops.roi._RoIAlignFn grad_share)
-            share = handoff.PoolerShare() if self.mask_on else None
-            # the mask branch's foreground count is read while the box branch
-            # is enqueued (the device never idles at the read)
-            pending = None
-            # (d2mi_roi_sample_take: the mask branch's fg-first inputs, fg and
-            # the foreground count made with the sampled rows)
-            fused = sampled.pop("_mask_prep", None)
-            fg = (fused[1] if fused is not None
-                  else self._mask_fg(sampled) if self.mask_on else None)  # (once per step)
-            count = fused[2] if fused is not None else None
-            defer = self.mask_on and self.mask_compact_rows and self.defer_mask_loss
-            prep = None
-            if self.mask_on and self.mask_compact_rows:
-                if not defer:
-                    pending = host_sync.start_read(count if count is not None else fg.sum())
-                # (deferred too, r5: in a replayed step these small gathers are
-                # issued inside graph A, under the box branch's kernels, not at
-                # graph B's head where the host's per-node submission outran them)
-                if fused is not None:
-                    gm = targets["gt_masks"]
-                    prep = (fused[0], gm.reshape(gm.shape[0] * gm.shape[1], *gm.shape[2:]), fg)
-                elif self.MASK_PREP_EARLY:
-                    prep = self._mask_prep(sampled, targets, fg)
-            losses = self._box_losses(feats, sampled, share)
-            if defer:
-                losses["loss_mask"] = DeferredMaskLoss(self, feats, sampled, targets, share, fg,
-                                                       prep, count)
-            elif self.mask_on:
-                losses["loss_mask"] = self._mask_loss(feats, sampled, targets, share, pending, fg,
-                                                      prep=prep)
-            return sampled, losses
-        pred = self._forward_box(feats, proposals, images.image_shapes)
-        pred = self.forward_with_given_boxes(features, pred)
-        return pred, {}
+        if not self.training:
+            pred = self._forward_box(feats, proposals, images.image_shapes)
+            return self.forward_with_given_boxes(features, pred), {}
+        if targets is None:
+            raise ValueError("ROI-head training needs targets")
+        sampled, fused = self._sample(
+            proposals, targets, self.mask_slots if self.mask_on and self.mask_compact_rows else 0)
+        plan = self._plan_mask(sampled, fused, targets)
+        return sampled, self._losses(feats, sampled, plan, images, targets)
+
+    def _defers(self):
+        return self.mask_loss_deferrable and self.mask_compact_rows and self.defer_mask_loss
+
+    def _plan_mask(self, sampled, fused, targets):
+        """The step's MaskPrep (None without a mask branch): the fused
+        sampler's, or the foreground flags with the per-row tensors made here
+        (MASK_PREP_EARLY) or left to _prepared.  With compact rows the count's
+        host read starts here, to run while the box branch is enqueued (the
+        device never idles at the read); a deferred mask loss starts none."""
+        if not self.mask_on:
+            return None
+        plan = fused if fused is not None else MaskPrep(self._mask_fg(sampled))  # (once per step)
+        if self.mask_compact_rows:
+            if not self._defers():
+                plan = plan._replace(pending=host_sync.start_read(plan.device_count()))
+            # (deferred too, r5: in a replayed step these small gathers are
+            # issued inside graph A, under the box branch's kernels, not at
+            # graph B's head where the host's per-node submission outran them)
+            if self.MASK_PREP_EARLY:
+                plan = self._prepared(plan, sampled, targets)
+        return plan
+
+    def _prepared(self, plan, sampled, targets):
+        if plan.boxes is not None:
+            return plan
+        return self._mask_prep(sampled, targets, plan.fg_slots)._replace(pending=plan.pending)
+
+    def _losses(self, feats, sampled, plan, images, targets):
+        # the box and mask poolers read the same p2..p5: one gradient map
+        # set for both backwards (ops.roi._RoIAlignFn grad_share)
+        share = handoff.PoolerShare() if self.mask_on else None
+        losses = self._box_losses(feats, sampled, images.image_shapes, targets, share)
+        if plan is not None and self._defers():
+            losses["loss_mask"] = DeferredMaskLoss(self, feats, sampled, targets, plan, share)
+        elif plan is not None:
+            losses["loss_mask"] = self._mask_loss(feats, sampled, targets, plan, share)
+        return losses
 
     def _box_features(self, x, boxes, valid):
         """The box head on the pooled rows of boxes [N, P, 4] / valid [N, P]
@@ -264,35 +334,31 @@ class StandardROIHeads(ROIHeads):
         return self.box_head(x)
 
     def _forward_box(self, feats, proposals, image_shapes):
-        boxes = proposals.boxes
-        valid = proposals.get_field("is_valid")
-        N, P = valid.shape
-        dev = boxes.device
-        img = _cached_index("img", N, P, dev)
-        slot = _cached_index("slot", N, P, dev)
-        slot = torch.where(valid.reshape(-1), slot, torch.full_like(slot, -1))
+        boxes, valid, img, slot, N, P = self._proposal_rows(proposals)
         x = self.box_pooler.pool(feats, boxes.reshape(-1, 4), img)
         x = self._box_features(x, boxes, valid)
+        return self._predict(x, boxes, img, slot, N, P, image_shapes)
+
+    def _predict(self, x, boxes, img, slot, N, P, image_shapes):
         logits, deltas = self.box_predictor(x)
-        ob, os_, oc, ov, _ = fast_rcnn_inference(
+        return self._detections(*fast_rcnn_inference(
             logits, deltas, boxes.reshape(-1, 4), img, slot, N, P, image_shapes,
             self.box2box_transform, self.test_score_thresh, self.test_nms_thresh,
-            self.test_detections_per_img, self.test_nms_cls_agnostic)
-        res = BoxList(ob)
-        res.add_field("scores", os_)
-        res.add_field("pred_classes", oc)
-        res.add_field("is_valid", ov)
-        res.set_tracking("image_shape", image_shapes)
-        return res
+            self.test_detections_per_img, self.test_nms_cls_agnostic)[:4], image_shapes)
 
-    def _box_losses(self, feats, sampled, grad_share=None):
+    def _box_losses(self, feats, sampled, image_shapes, targets, grad_share=None):
+        # (image_shapes and targets: the step's context, for CascadeROIHeads)
         boxes = sampled["boxes"]
         N, S = boxes.shape[:2]
         img = _cached_index("img", N, S, boxes.device)
         x = self.box_pooler.pool(feats, boxes.reshape(-1, 4).contiguous(), img,
                                  grad_share=grad_share)
-        logits, deltas = self.box_predictor(self._box_features(x, boxes, sampled["is_valid"]))
-        return fast_rcnn_losses(logits, deltas, boxes.reshape(-1, 4), sampled["gt_classes"].reshape(-1),
+        return self._predictor_losses(self._box_features(x, boxes, sampled["is_valid"]), sampled)
+
+    def _predictor_losses(self, x, sampled):
+        logits, deltas = self.box_predictor(x)
+        return fast_rcnn_losses(logits, deltas, sampled["boxes"].reshape(-1, 4),
+                                sampled["gt_classes"].reshape(-1),
                                 sampled["gt_boxes"].reshape(-1, 4), sampled["is_valid"].reshape(-1),
                                 self.box2box_transform, self.smooth_l1_beta)
 
@@ -301,9 +367,8 @@ class StandardROIHeads(ROIHeads):
         valid and not background.  (A sampled slot is a positive, class in
         [0, K), or a negative, class K -- the ignored -1 rows are never
         sampled -- so `class < K` is the reference's `!= -1 and != bg` there.)"""
-        F_ = int(self.batch_size_per_image * self.positive_sample_fraction)
-        return (sampled["is_valid"][:, :F_]
-                & (sampled["gt_classes"][:, :F_] < self.num_classes)).reshape(-1)
+        return (sampled["is_valid"][:, :self.mask_slots]
+                & (sampled["gt_classes"][:, :self.mask_slots] < self.num_classes)).reshape(-1)
 
     def mask_rows(self, nfg, slots):
         """Rows the compacted mask branch runs for nfg foreground proposals out
@@ -313,13 +378,12 @@ class StandardROIHeads(ROIHeads):
         return min(slots, max(b, -(-nfg // b) * b))
 
     def _mask_prep(self, sampled, targets, fg=None):
-        """The mask branch's per-slot inputs over the first int(S *
-        POSITIVE_FRACTION) slots per image, and (compact rows) the slots in
-        fg-first order -- everything that does not need the foreground count,
-        so the host issues it before the count's read."""
-        F_ = int(self.batch_size_per_image * self.positive_sample_fraction)
+        """The MaskPrep of the sampled rows, made with tensor ops: the per-slot
+        inputs over the first int(S * POSITIVE_FRACTION) slots per image, and
+        (compact rows) the slots in fg-first order -- everything that does not
+        need the foreground count, so the host issues it before the count's read."""
+        N, F_ = sampled["boxes"].shape[0], self.mask_slots
         boxes = sampled["boxes"][:, :F_].reshape(-1, 4)
-        N = sampled["boxes"].shape[0]
         dev = boxes.device
         cls = sampled["gt_classes"][:, :F_].reshape(-1)
         fg = self._mask_fg(sampled) if fg is None else fg
@@ -328,20 +392,19 @@ class StandardROIHeads(ROIHeads):
         G = gm.shape[1]
         mind = (sampled["gt_index"][:, :F_] + _cached_index("base", N, G, dev)).reshape(-1)
         gt_boxes = sampled["gt_boxes"][:, :F_].reshape(-1, 4)
-        ts = (boxes, cls, fg, img, mind, gt_boxes)
+        rows = (boxes, cls, fg, img, mind, gt_boxes)
         if self.mask_compact_rows:
             # fg rows first, each group in index order (a stable sort of ~fg);
             # the count only decides how many of them run (a view)
             order = torch.argsort((~fg).to(torch.uint8), stable=True)
-            ts = tuple(t[order] for t in ts)
-        return ts, gm.reshape(N * G, *gm.shape[2:]), fg
+            rows = tuple(t[order] for t in rows)
+        return MaskPrep(fg, *rows, gt_masks=gm.flatten(0, 1))
 
-    def _mask_loss(self, feats, sampled, targets, grad_share=None, pending=None, fg=None,
-                   rows=None, prep=None):
+    def _mask_loss(self, feats, sampled, targets, plan, grad_share=None, rows=None):
         """_forward_mask training branch (roi_heads.py:594-600) over the first
         int(S * POSITIVE_FRACTION) slots per image, which hold every sampled
         foreground proposal (select_foreground_proposals, roi_heads.py:35-62)."""
-        ts, gm, fg_all = prep if prep is not None else self._mask_prep(sampled, targets, fg)
+        plan = self._prepared(plan, sampled, targets)
         if self.mask_compact_rows:
             # The reference runs the mask head on the foreground proposals only
             # (select_foreground_proposals, roi_heads.py:35-62 + :594-600).  One
@@ -350,18 +413,20 @@ class StandardROIHeads(ROIHeads):
             # with masked-out rows, which bounds the number of distinct shapes.
             # (rows given: a deferred mask loss, DeferredMaskLoss.compute)
             if rows is None:
-                nfg = (host_sync.finish_read(pending) if pending is not None
-                       else host_sync.read_ints(fg_all.sum()))[0]
-                rows = self.mask_rows(nfg, fg_all.numel())
-            R = rows
-            ts = tuple(t[:R] for t in ts)
-            self.last_mask_rows = R
-        else:
-            self.last_mask_rows = int(ts[0].shape[0])
-        boxes, cls, fg, img, mind, gt_boxes = ts
-        x = self.mask_pooler.pool(feats, boxes.contiguous(), img, grad_share=grad_share)
+                rows = self.mask_rows(host_sync.finish_read(plan.pending)[0], plan.fg_slots.numel())
+            plan = plan.head(rows)
+        self.last_mask_rows = int(plan.boxes.shape[0])
+        x = self.mask_pooler.pool(feats, plan.boxes.contiguous(), plan.img, grad_share=grad_share)
         _, logits = self.mask_head(x)
-        return mask_rcnn_loss(logits, boxes, gt_boxes, cls, gm, mind, fg, self.use_mini_masks)
+        return self._mask_rcnn_loss(logits, plan)
+
+    def _mask_rcnn_loss(self, logits, plan):
+        return mask_rcnn_loss(logits, plan.boxes, plan.gt_boxes, plan.classes, plan.gt_masks,
+                              plan.gt_mask_index, plan.fg, self.use_mini_masks)
+
+    def _mask_outputs(self, feats, boxes, img):
+        """The mask head's (deconv, logits) on boxes [R, 4] of images img [R]."""
+        return self.mask_head(self.mask_pooler.pool(feats, boxes, img))
 
     def forward_with_given_boxes(self, features, instances, image_shape=None):
         assert not self.training
@@ -372,234 +437,10 @@ class StandardROIHeads(ROIHeads):
         boxes = instances.boxes
         N, D = boxes.shape[:2]
         img = _cached_index("img", N, D, boxes.device)
-        x = self.mask_pooler.pool(feats, boxes.reshape(-1, 4), img)
-        deconv, logits = self.mask_head(x)
+        _, logits = self._mask_outputs(feats, boxes.reshape(-1, 4), img)
         masks = mask_rcnn_inference(logits, instances.get_field("pred_classes").reshape(-1))
         valid = instances.get_field("is_valid").reshape(-1)
         masks = masks * valid[:, None, None].to(masks.dtype)
         instances.add_field("pred_masks", masks.reshape(N, D, *masks.shape[1:]))
         return instances
 
-
-@ROI_HEADS_REGISTRY.register()
-class Res5ROIHeads(StandardROIHeads):
-    """The C4 head (lib/modeling/roi_heads/roi_heads.py:261-408): one pooler on
-    res4, the res5 stage over the pooled rows, the box predictor on their
-    spatial mean and the mask head on rows of the same res5 output.
-
-    The sampling, the fg-first mask rows, the foreground-count read and the
-    MASK_ROW_BUCKET padding are StandardROIHeads'; there is one pooling and one
-    res5 per training step.  The mean and the mask rows' gather are one launch
-    (ops.res5_pool), and so is their backward.  Training is eager: the count
-    read sits inside the forward (engine.graphed refuses the head).
-
-    ELIDE_STRIDE: with STRIDE_IN_1X1, an even POOLER_RESOLUTION 2n and
-    POOLER_SAMPLING_RATIO 0, block_1's two stride-2 1x1 convs read only the
-    even grid of the 2n x 2n crop, which is itself an n x n crop of a modified
-    box (_even_grid_boxes): pool that and run block_1 at stride 1, the same
-    weights.  Any other setting pools the full crop.
-    Deviation: the reference's training branch reads an
-    undefined name and hands the mask head's tuple to the loss; the evident
-    intent, the loss on the head's mask logits, is what runs here."""
-    # On by default: ahead of the literal path in tools/res5_ab.py (1.02x at
-    # inference on 1000 proposals, 6.4x in training on 2 x 512 rows:
-    # profiles/res5_ab.json, DESIGN.md section 5 "C4 head").
-    ELIDE_STRIDE = True
-    # (the pooled map has one reader, the head: no RPN / pooler gradient pair)
-    merged_pool_backward = False
-
-    def __init__(self, cfg, input_shape, **kwargs):
-        ROIHeads.__init__(self, cfg, input_shape, **kwargs)
-        from ..backbone.resnet import BottleneckBlock, Stage, resnet_arg_scope
-        from ...layers.convolutional import FoldGroup
-        assert len(self.in_features) == 1
-        b, r = cfg.MODEL.ROI_BOX_HEAD, cfg.MODEL.RESNETS
-        res = b.POOLER_RESOLUTION
-        scales = (1.0 / self.feature_strides[self.in_features[0]],)
-        self.mask_on = cfg.MODEL.MASK_ON
-        self.pooler = ROIPooler(res, scales, b.POOLER_SAMPLING_RATIO, b.POOLER_TYPE)
-        assert not r.DEFORM_ON_PER_STAGE[-1], "Deformable conv is not yet supported in res5 head."
-        out_channels = r.RES2_OUT_CHANNELS * 8  # res5 is 8x res2
-        kw = {"in_channels": out_channels // 2, "out_channels": out_channels,
-              "bottleneck_channels": r.NUM_GROUPS * r.WIDTH_PER_GROUP * 8,
-              "num_groups": r.NUM_GROUPS, "stride_in_1x1": r.STRIDE_IN_1X1}
-        with resnet_arg_scope(False, r.NORM):
-            self.res5 = Stage(BottleneckBlock, block_kwargs=kw, num_blocks=3, first_stride=2,
-                              scope="res5")
-        FoldGroup.attach(self.res5)
-        self.out_channels = out_channels
-        # the elision's n x n pooler, where its conditions hold
-        self.half_pooler = None
-        if r.STRIDE_IN_1X1 and b.POOLER_SAMPLING_RATIO == 0 and res % 2 == 0:
-            self.half_pooler = ROIPooler(res // 2, scales, 0, b.POOLER_TYPE)
-        self.box_predictor = FastRCNNOutputLayers(out_channels, self.num_classes,
-                                                  self.cls_agnostic_bbox_reg, scope="fastrcnn")
-        self.mask_compact_rows = True
-        self.defer_mask_loss = False
-        self.last_mask_rows = None
-        if self.mask_on:
-            self.use_mini_masks = cfg.TRANSFORM.RESIZE.USE_MINI_MASKS
-            self.mask_head = build_mask_head(
-                cfg, ShapeSpec(channels=out_channels, width=res, height=res), scope="mask_head")
-
-    def elides(self):
-        return self.ELIDE_STRIDE and self.half_pooler is not None
-
-    def _even_grid_boxes(self, boxes):
-        """The boxes whose n x n crop is the even grid (2i, 2j) of ``boxes``'
-        2n x 2n crop.  ROIAlignV2 (aligned, sample i at y0 + (i + 1/2) h / 2n):
-        the same size, moved up and left by a quarter bin of the n x n crop,
-        (h / 4n, w / 4n).  ROIAlign (tf.image.crop_and_resize spacing h / (2n -
-        1) from y0): the same corner, the size scaled by (2n - 2) / (2n - 1)."""
-        n = self.half_pooler.output_size[0]
-        hw = boxes[:, 2:] - boxes[:, :2]
-        if self.pooler.aligned:
-            q = hw / (4.0 * n)
-            return torch.cat([boxes[:, :2] - q, boxes[:, 2:] - q], 1)
-        return torch.cat([boxes[:, :2], boxes[:, :2] + hw * ((2.0 * n - 2.0) / (2.0 * n - 1.0))], 1)
-
-    def _pool(self, feats, boxes, img):
-        """The res5 input of boxes [R, 4]: (rows [R, h, w, C], the stride block_1 runs at)."""
-        pooler, stride = self.pooler, None
-        if self.elides():
-            pooler, stride, boxes = self.half_pooler, 1, self._even_grid_boxes(boxes)
-        if feats[0].is_cuda:
-            return pooler.pool(feats, boxes.contiguous(), img), stride
-        from ...layers.ops import BOX_MODE_ALIGNED, BOX_MODE_UNALIGNED
-        from .res5_dense import crop_and_resize_dense
-        if pooler.sampling_ratio > 0:
-            raise NotImplementedError("the crop's tensor formulation takes one sample per bin")
-        mode = BOX_MODE_ALIGNED if pooler.aligned else BOX_MODE_UNALIGNED
-        return crop_and_resize_dense(feats[0], boxes, img, pooler.output_size, pooler.scales[0],
-                                     mode), stride
-
-    def _res5(self, x, stride=None):
-        if not x.is_cuda:
-            from .res5_dense import stage_dense
-            return stage_dense(self.res5, x, stride)
-        if stride is None:
-            return self.res5(x)
-        # block_1 at ``stride``: its strided convs read their stride at call time
-        strided = [c for c in (self.res5.blocks[0].shortcut, self.res5.blocks[0].conv1)
-                   if c is not None and c.stride > 1]
-        saved = [c.stride for c in strided]
-        try:
-            for c in strided:
-                c.stride = stride
-            return self.res5(x)
-        finally:
-            for c, s in zip(strided, saved):
-                c.stride = s
-
-    def _shared_roi_transform(self, feats, boxes, img):
-        x, stride = self._pool(feats, boxes, img)
-        return self._res5(x, stride)
-
-    def _pool_gather(self, x, dst=None, rows=0):
-        """(the spatial mean [R, C], the rows dst names [rows, h, w, C] or None)
-        of the res5 output x [R, h, w, C]."""
-        R, h, w, C = x.shape
-        fn = ops.res5_pool if x.is_cuda and ops.res5.FUSED_POOL and C % 4 == 0 \
-            else ops.res5_pool_dense
-        pooled, y = fn(x.reshape(R, h * w, C), dst, rows)
-        return pooled, (y.reshape(rows, h, w, C) if y is not None else None)
-
-    def _mask_head(self, x):
-        if x.is_cuda:
-            return self.mask_head(x)
-        from .res5_dense import mask_head_dense
-        return mask_head_dense(self.mask_head, x)
-
-    def _mask_dst(self, fg, rows, N, S):
-        """dst [N*S] int32 of the gather: mask row m < rows is the m-th slot
-        of _mask_prep's order (fg first, each group in slot order) over the
-        first F slots per image; slot k of that [N, F] layout is sampled row
-        (k // F) * S + k % F."""
-        F_ = fg.numel() // N
-        order = torch.argsort((~fg).to(torch.uint8), stable=True)[:rows]
-        src = torch.div(order, F_, rounding_mode="floor") * S + order % F_
-        dst = torch.full((N * S,), -1, dtype=torch.int32, device=fg.device)
-        dst[src] = torch.arange(rows, dtype=torch.int32, device=fg.device)
-        return dst
-
-    def call(self, images, features, proposals, targets=None):
-        feats = [features[f] for f in self.in_features]
-        if not self.training:
-            pred = self._forward_box(feats, proposals, images.image_shapes)
-            return self.forward_with_given_boxes(features, pred), {}
-        if targets is None:
-            raise ValueError("ROI-head training needs targets")
-        sampled = self.label_and_sample_proposals(proposals, targets)
-        fused = sampled.pop("_mask_prep", None)
-        pending = prep = None
-        if self.mask_on:
-            fg = fused[1] if fused is not None else self._mask_fg(sampled)
-            # the foreground count is read while the pooling and res5 are enqueued
-            pending = host_sync.start_read(fused[2] if fused is not None else fg.sum())
-            if fused is not None:
-                gm = targets["gt_masks"]
-                prep = (fused[0], gm.reshape(gm.shape[0] * gm.shape[1], *gm.shape[2:]), fg)
-            else:
-                prep = self._mask_prep(sampled, targets, fg)
-        boxes = sampled["boxes"]
-        N, S = boxes.shape[:2]
-        img = _cached_index("img", N, S, boxes.device)
-        x = self._shared_roi_transform(feats, boxes.reshape(-1, 4), img)
-        dst, rows = None, 0
-        if self.mask_on:
-            ts, gm, fg_all = prep
-            rows = self.mask_rows(host_sync.finish_read(pending)[0], fg_all.numel())
-            self.last_mask_rows = rows
-            dst = self._mask_dst(fg_all, rows, N, S)
-        pooled, mask_x = self._pool_gather(x, dst, rows)
-        logits, deltas = self.box_predictor(pooled)
-        losses = fast_rcnn_losses(logits, deltas, boxes.reshape(-1, 4),
-                                  sampled["gt_classes"].reshape(-1),
-                                  sampled["gt_boxes"].reshape(-1, 4),
-                                  sampled["is_valid"].reshape(-1), self.box2box_transform,
-                                  self.smooth_l1_beta)
-        if self.mask_on:
-            mboxes, cls, fg, _, mind, gt_boxes = (t[:rows] for t in ts)
-            _, mask_logits = self._mask_head(mask_x)
-            losses["loss_mask"] = mask_rcnn_loss(mask_logits, mboxes, gt_boxes, cls, gm, mind, fg,
-                                                 self.use_mini_masks)
-        return sampled, losses
-
-    def _forward_box(self, feats, proposals, image_shapes):
-        boxes = proposals.boxes
-        valid = proposals.get_field("is_valid")
-        N, P = valid.shape
-        dev = boxes.device
-        img = _cached_index("img", N, P, dev)
-        slot = _cached_index("slot", N, P, dev)
-        slot = torch.where(valid.reshape(-1), slot, torch.full_like(slot, -1))
-        x = self._shared_roi_transform(feats, boxes.reshape(-1, 4), img)
-        logits, deltas = self.box_predictor(self._pool_gather(x)[0])
-        ob, os_, oc, ov, _ = fast_rcnn_inference(
-            logits, deltas, boxes.reshape(-1, 4), img, slot, N, P, image_shapes,
-            self.box2box_transform, self.test_score_thresh, self.test_nms_thresh,
-            self.test_detections_per_img, self.test_nms_cls_agnostic)
-        res = BoxList(ob)
-        res.add_field("scores", os_)
-        res.add_field("pred_classes", oc)
-        res.add_field("is_valid", ov)
-        res.set_tracking("image_shape", image_shapes)
-        return res
-
-    def forward_with_given_boxes(self, features, instances, image_shape=None):
-        assert not self.training
-        assert instances.has_field("pred_classes")
-        if not self.mask_on:
-            return instances
-        feats = [features[f] for f in self.in_features]
-        boxes = instances.boxes
-        N, D = boxes.shape[:2]
-        img = _cached_index("img", N, D, boxes.device)
-        # the detections through the same pooler and res5 (_shared_roi_transform)
-        x = self._shared_roi_transform(feats, boxes.reshape(-1, 4), img)
-        _, logits = self._mask_head(x)
-        masks = mask_rcnn_inference(logits, instances.get_field("pred_classes").reshape(-1))
-        valid = instances.get_field("is_valid").reshape(-1)
-        masks = masks * valid[:, None, None].to(masks.dtype)
-        instances.add_field("pred_masks", masks.reshape(N, D, *masks.shape[1:]))
-        return instances

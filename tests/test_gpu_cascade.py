@@ -343,6 +343,16 @@ def test_cascade_heads_training_losses_match_the_oracle_per_stage(dev):
         assert seen == {0, 80}  # foreground and background rows took part
 
 
+def test_cascade_training_call_leaves_no_state_on_the_module(dev):
+    """The step's image shapes and targets reach the stages as arguments: a
+    training call adds no attribute to the head and removes none."""
+    heads = _heads(dev, True)
+    images, feats, props, targets = _head_inputs(dev)
+    before = set(vars(heads))
+    _, losses = heads(images, feats, props, targets)
+    assert "loss_cls_stage2" in losses and set(vars(heads)) == before
+
+
 def test_cascade_heads_scale_the_pooled_feature_gradient_by_one_third(dev, monkeypatch):
     """The gradient reaching each stage's pooled features through
     CascadeROIHeads is 1/3 of the gradient with the scale taken out (one f32

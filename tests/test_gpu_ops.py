@@ -1830,17 +1830,18 @@ def test_roi_sample_take_matches_torch_glue(dev, case):
         ref = heads.label_and_sample_proposals(pl, targets)
         rh.FUSED_SAMPLE_TAKE = True
         torch.manual_seed(11)
-        got = heads.label_and_sample_proposals(pl, targets)
+        got, fused = heads._sample(pl, targets, heads.mask_slots)
     finally:
         rh.FUSED_SAMPLE_TAKE = True
-    fused = got.pop("_mask_prep")
-    assert sorted(got) == sorted(ref)
+    assert sorted(got) == sorted(ref) == ["boxes", "gt_boxes", "gt_classes", "gt_index", "is_valid"]
     for k in ref:
         assert got[k].dtype == ref[k].dtype and torch.equal(got[k], ref[k]), k
-    ts, _, fg = heads._mask_prep(ref, targets)
-    for a, b in zip(fused[0], ts):
-        assert a.dtype == b.dtype and torch.equal(a, b)
-    assert torch.equal(fused[1], fg)
-    assert int(fused[2].item()) == int(fg.sum().item())
+    want = heads._mask_prep(ref, targets)
+    for name in rh.MaskPrep.ROWS + ("gt_masks",):
+        a, b = getattr(fused, name), getattr(want, name)
+        assert a.dtype == b.dtype and torch.equal(a, b), name
+    fg = want.fg_slots
+    assert torch.equal(fused.fg_slots, fg)
+    assert int(fused.count.item()) == int(fg.sum().item())
     if case == "empty_gt_image":
         assert not bool(fg[fg.numel() // 2:].any())

@@ -220,6 +220,16 @@ def test_cpu_training_forward_with_an_image_without_foreground():
     assert torch.isfinite(f.grad).all()
 
 
+def test_training_with_fixed_mask_rows_is_refused():
+    """The mask rows are gathered fg-first from the shared res5 output; the
+    fixed-row setting orders their targets by slot, so it is an error."""
+    _, head = ref.narrow_head(ROOT)
+    head.mask_compact_rows = False
+    feat, proposals, targets, shapes = ref.make_case()
+    with pytest.raises(NotImplementedError, match="compacted fg-first rows only"):
+        _cpu_losses(head, feat, proposals, targets, shapes)
+
+
 def test_faster_rcnn_c4_head_has_no_mask_branch():
     _, head = ref.narrow_head(ROOT, mask_on=False)
     feat, proposals, targets, shapes = ref.make_case()
