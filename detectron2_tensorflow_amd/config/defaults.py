@@ -6,8 +6,8 @@ GeneralizedRCNN / SingleStageDetector / PanopticFPN / SemanticSegmentor /
 ResNet / DarkNet53 / FPN / RPN / ROI heads / RetinaNet / SOLO / YOLOv4 / the
 semantic head, SOLVER, TRANSFORM, TEST, ...), so the reference YAML files
 merge without unknown-key errors.  MODEL.YOLOV4 (:671-682) is read by the
-YOLOv4 head, which runs inference only: CLS_NORMALIZER and IOU_NORMALIZER
-belong to its loss and are kept for the YAMLs.  Subsystems this build does
+YOLOv4 head: CLS_NORMALIZER and IOU_NORMALIZER weigh its class and box
+losses (single_stage_heads/yolov4_outputs.py).  Subsystems this build does
 not implement (SpineNet, the panoptic evaluator, data augmentation, TFRecord
 readers) keep only the keys the shipped YAMLs set.
 """

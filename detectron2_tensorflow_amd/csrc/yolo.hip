@@ -28,62 +28,14 @@
 //
 // The decode, sigmoid, score and class expressions of the two YOLO entry
 // points are the same __device__ functions, so their bits agree.
-#include "detect.h"
 #include "wave.h"
+#include "yolo.h"
 
 namespace d2mi {
 namespace {
 
-constexpr int kYB = 256;    // predictions per score / compact workgroup
 constexpr int kNmsWG = 1024;
 constexpr int kTile = 64;
-constexpr int kYoloMaxA = 12;  // anchors per cell of a YOLO level (YoloGeo's cell tables)
-
-struct YoloGeo {
-  const float* ptr[D2MI_MAX_LEVELS];  // level l: [N, H, W, A * (5 + K)]
-  int32_t H[D2MI_MAX_LEVELS], W[D2MI_MAX_LEVELS];
-  int32_t p0[D2MI_MAX_LEVELS + 1];    // per-image prefix of predictions (H W A)
-  float stride[D2MI_MAX_LEVELS];
-  float cell_h[D2MI_MAX_LEVELS][kYoloMaxA], cell_w[D2MI_MAX_LEVELS][kYoloMaxA];
-  float s[D2MI_MAX_LEVELS], half[D2MI_MAX_LEVELS];  // scale_yx, 0.5 * (scale_yx - 1)
-  int32_t L, A, K, N, P;
-  int32_t nb;                         // score blocks per image
-};
-
-struct PredAt {
-  const float* row;  // the prediction's 5 + K logits
-  int l, a, h, w;
-};
-
-// Prediction p of image n: level-major, then (h, w, a) (the reshape to
-// [N, -1, ...] and concat of yolov4_outputs.py:247-260).
-__device__ __forceinline__ PredAt locate(const YoloGeo& g, int n, int p) {
-  int l = 0;
-  while (l + 1 < g.L && g.p0[l + 1] <= p) ++l;
-  const int j = p - g.p0[l];
-  const int cell = j / g.A;
-  PredAt q;
-  q.l = l;
-  q.a = j - cell * g.A;
-  q.h = cell / g.W[l];
-  q.w = cell - q.h * g.W[l];
-  q.row = g.ptr[l] + ((int64_t)n * (g.p0[l + 1] - g.p0[l]) + j) * (int64_t)(5 + g.K);
-  return q;
-}
-
-// yolov4_outputs.py:236-241, term by term in float32 (no contraction):
-// anchors[:, :2] is the grid index (the cell anchors start at 0).
-__device__ __forceinline__ float4 yolo_box(const YoloGeo& g, const PredAt& q) {
-  const float r0 = q.row[0], r1 = q.row[1], r2 = q.row[2], r3 = q.row[3];
-  const float s = g.s[q.l], half = g.half[q.l], stride = g.stride[q.l];
-  const float dy = s * sigmoidf_tf(r0) - half;
-  const float dx = s * sigmoidf_tf(r1) - half;
-  const float y = ((float)q.h + dy) * stride;
-  const float x = ((float)q.w + dx) * stride;
-  const float hh = expf(r2) * g.cell_h[q.l][q.a];
-  const float ww = expf(r3) * g.cell_w[q.l][q.a];
-  return make_float4(y - 0.5f * hh, x - 0.5f * ww, y + 0.5f * hh, x + 0.5f * ww);
-}
 
 __device__ __forceinline__ float yolo_conf(const float* row) { return sigmoidf_tf(row[4]); }
 
@@ -336,7 +288,9 @@ struct YoloWs {
   }
 };
 
-// Predictions per image, or -1 when the sizes are out of range (message set).
+}  // namespace
+
+// (declared in yolo.h: yolo_loss.hip builds its tables with them too)
 int64_t yolo_total(int N, int L, const int32_t* level_hw, int A) {
   D2MI_REQUIRE(N >= 1, "N=%d out of range", N);
   D2MI_REQUIRE(L >= 1 && L <= D2MI_MAX_LEVELS, "L=%d out of range [1,%d]", L, D2MI_MAX_LEVELS);
@@ -353,12 +307,12 @@ int64_t yolo_total(int N, int L, const int32_t* level_hw, int A) {
   return P;
 }
 
-int make_geo(YoloGeo& g, const float* const* logits, const int32_t* level_hw, const float* strides,
-             const float* cell_hw, const float* scale_yx, int L, int A, int K, int N) {
+int make_geo_tables(YoloGeo& g, const int32_t* level_hw, const float* strides, const float* cell_hw,
+                    const float* scale_yx, int L, int A, int K, int N) {
   D2MI_REQUIRE(K >= 1, "K=%d out of range", K);
   const int64_t P = yolo_total(N, L, level_hw, A);
   if (P < 0) return -1;
-  D2MI_REQUIRE(logits && strides && cell_hw && scale_yx, "null host array");
+  D2MI_REQUIRE(strides && cell_hw, "null host array");
   g = YoloGeo{};
   g.L = L;
   g.A = A;
@@ -368,14 +322,14 @@ int make_geo(YoloGeo& g, const float* const* logits, const int32_t* level_hw, co
   g.nb = (int32_t)((P + kYB - 1) / kYB);
   g.p0[0] = 0;
   for (int l = 0; l < L; ++l) {
-    g.ptr[l] = logits[l];
-    D2MI_REQUIRE(g.ptr[l] != nullptr, "level %d logits are null", l);
     g.H[l] = level_hw[2 * l];
     g.W[l] = level_hw[2 * l + 1];
     g.p0[l + 1] = g.p0[l] + g.H[l] * g.W[l] * A;
     g.stride[l] = strides[l];
-    g.s[l] = scale_yx[2 * l];
-    g.half[l] = scale_yx[2 * l + 1];
+    if (scale_yx) {
+      g.s[l] = scale_yx[2 * l];
+      g.half[l] = scale_yx[2 * l + 1];
+    }
     for (int a = 0; a < A; ++a) {
       g.cell_h[l][a] = cell_hw[(l * A + a) * 2];
       g.cell_w[l][a] = cell_hw[(l * A + a) * 2 + 1];
@@ -383,6 +337,22 @@ int make_geo(YoloGeo& g, const float* const* logits, const int32_t* level_hw, co
   }
   return 0;
 }
+
+int make_geo(YoloGeo& g, const float* const* logits, const int32_t* level_hw, const float* strides,
+             const float* cell_hw, const float* scale_yx, int L, int A, int K, int N) {
+  D2MI_REQUIRE(K >= 1, "K=%d out of range", K);
+  if (yolo_total(N, L, level_hw, A) < 0) return -1;
+  D2MI_REQUIRE(logits && strides && cell_hw && scale_yx, "null host array");
+  int rc = make_geo_tables(g, level_hw, strides, cell_hw, scale_yx, L, A, K, N);
+  if (rc) return rc;
+  for (int l = 0; l < L; ++l) {
+    g.ptr[l] = logits[l];
+    D2MI_REQUIRE(g.ptr[l] != nullptr, "level %d logits are null", l);
+  }
+  return 0;
+}
+
+namespace {
 
 // --------------------------------------------------------------------- SPP
 // One workgroup per (channel chunk, output row h, image): the column maxima

@@ -33,7 +33,7 @@ from .detect import (ACT_LEAKY_RELU, ACT_MISH, activation_, fast_rcnn_inference,
                      yolov4_predictions)
 from .fold import fold_frozen_bn, fold_frozen_bn_many  # noqa: F401
 from .losses import (fast_rcnn_loss, mask_loss, retina_loss, rpn_loss,  # noqa: F401
-                     scale_gradient)
+                     scale_gradient, yolov4_loss)
 from .norm import (batch_norm_train, group_norm, group_norm_levels, resize_bilinear,  # noqa: F401
                    resize_bilinear_grad)
 from .relation import relation_attention, relation_supported  # noqa: F401

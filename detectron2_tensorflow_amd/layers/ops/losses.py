@@ -1,10 +1,11 @@
-"""The fused training losses: RPN, Fast R-CNN, mask and RetinaNet
-(csrc/rpn_loss.hip, roi_losses.hip, retina_loss.hip), and the cascade's
-gradient scaling."""
+"""The fused training losses: RPN, Fast R-CNN, mask, RetinaNet and YOLOv4
+(csrc/rpn_loss.hip, roi_losses.hip, retina_loss.hip, yolo_loss.hip), and the
+cascade's gradient scaling."""
 import torch
 
 from ... import _C
 from ._common import _f32c, _mask_u8
+from .detect import _yolo_levels, yolo_host_arrays
 
 
 class _ScaleGradFn(torch.autograd.Function):
@@ -269,3 +270,96 @@ def retina_loss(cls_levels, box_levels, anchors, gt_boxes, gt_classes, matches, 
             tuple(float(v) for v in weights))
     return _RetinaLossFn.apply(conf, anchors, gt_boxes, gt_classes, matches, labels,
                                *cls_levels, *box_levels)
+
+
+class _YoloLossFn(torch.autograd.Function):
+    """(conf, cls, box) losses of YOLOV4Outputs.losses over the head's
+    per-level logits (d2mi_yolov4_loss_fwd / _bwd, csrc/yolo_loss.hip);
+    differentiable w.r.t. every level's logits.  Also returns the counts of
+    positives and negatives (no gradient)."""
+
+    @staticmethod
+    def forward(ctx, conf, gt_boxes, gt_classes, valid, slot, owner, state, *logits):
+        geo, K, image_area, thr, cls_norm, iou_norm = conf
+        lhw, st, chw, sc, L, A = geo
+        N, G = valid.shape
+        dev = logits[0].device
+        lib = _C.lib()
+        nb = lib.d2mi_yolov4_loss_blocks()
+        part = torch.empty((N * nb, 5), dtype=torch.float64, device=dev)
+        rc = lib.d2mi_yolov4_loss_fwd(
+            _C.host_array(_C.c_void_p, [t.data_ptr() for t in logits]), lhw, st, chw, sc, L, A, K,
+            N, _C.ptr(gt_boxes), _C.ptr(gt_classes), _C.ptr(valid), G, _C.ptr(slot),
+            _C.ptr(owner), image_area, thr, iou_norm, _C.ptr(part), _C.ptr(state),
+            _C.stream_of(dev))
+        _C.check(rc, "d2mi_yolov4_loss_fwd")
+        ctx.save_for_backward(gt_boxes, gt_classes, slot, owner, state, *logits)
+        ctx.conf = conf
+        ctx.set_materialize_grads(False)  # a missing gradient is a zero one (null pointer)
+        # fixed-size reduction of the float64 partials (deterministic order)
+        out = part.sum(0)
+        # 1 / N and CLS_NORMALIZER / N (yolov4_outputs.py:288, :318); the box
+        # weight carries IOU_NORMALIZER / N per element (:309)
+        conf_loss = (out[0] * (1.0 / N)).float()
+        cls_loss = (out[1] * (cls_norm / N)).float()
+        npos, nneg = out[3].to(torch.int64), out[4].to(torch.int64)
+        ctx.mark_non_differentiable(npos, nneg)
+        return conf_loss, cls_loss, out[2].float(), npos, nneg
+
+    @staticmethod
+    def backward(ctx, g_conf, g_cls, g_box, _gp, _gn):
+        gt_boxes, gt_classes, slot, owner, state, *logits = ctx.saved_tensors
+        geo, K, image_area, thr, cls_norm, iou_norm = ctx.conf
+        lhw, st, chw, sc, L, A = geo
+        N, G = slot.shape
+        dev = logits[0].device
+        d = [torch.empty_like(t) for t in logits]
+        g_conf = _f32c(g_conf) if g_conf is not None else None
+        g_cls = _f32c(g_cls) if g_cls is not None else None
+        g_box = _f32c(g_box) if g_box is not None else None
+        rc = _C.lib().d2mi_yolov4_loss_bwd(
+            _C.host_array(_C.c_void_p, [t.data_ptr() for t in logits]),
+            _C.host_array(_C.c_void_p, [t.data_ptr() for t in d]), lhw, st, chw, sc, L, A, K, N,
+            _C.ptr(gt_boxes), _C.ptr(gt_classes), G, _C.ptr(slot), _C.ptr(owner), _C.ptr(state),
+            image_area, iou_norm, 1.0 / N, cls_norm / N, _C.ptr(g_conf), _C.ptr(g_cls),
+            _C.ptr(g_box), _C.stream_of(dev))
+        _C.check(rc, "d2mi_yolov4_loss_bwd")
+        return (None,) * 7 + tuple(d)
+
+
+def yolov4_loss(pred_logits, strides, cell_anchors, scale_yx, num_classes, gt_boxes, gt_classes,
+                valid, image_hw, iou_threshold, cls_normalizer, iou_normalizer, debug=None):
+    """Fused YOLOv4 targets and losses (yolov4_outputs.py:59-206, :266-329;
+    d2mi_yolov4_assign + d2mi_yolov4_loss_fwd / _bwd): pred_logits[l]
+    [N, H, W, A * (5 + K)], gt_boxes [N, G, 4], gt_classes [N, G], valid
+    [N, G] = is_valid & ~crowd & ~difficult, image_hw the padded batch
+    tensor's (H, W) -> (conf_loss, cls_loss, box_loss, num_pos, num_neg),
+    device tensors, no host synchronisation.  ``debug``: a dict that receives
+    slot [N, G] and owner [N, P] (int32) and state [N, P] (uint8: 0 neither,
+    1 negative, 2 positive)."""
+    hw = [(t.shape[1], t.shape[2]) for t in pred_logits]
+    geo = yolo_host_arrays(hw, strides, cell_anchors, scale_yx)
+    lhw, st, chw, sc, L, A = geo
+    logits, N = _yolo_levels(pred_logits, num_classes, A)
+    dev = logits[0].device
+    gt_boxes = _f32c(gt_boxes)
+    gt_classes = gt_classes.to(torch.int64).contiguous()
+    valid = _mask_u8(valid)
+    _C.require_device(gt_boxes, gt_classes, valid)
+    G = valid.shape[1]
+    if gt_boxes.shape != (N, G, 4) or gt_classes.shape != (N, G) or valid.shape[0] != N:
+        raise ValueError(f"yolov4 loss: gt_boxes {tuple(gt_boxes.shape)} / gt_classes "
+                         f"{tuple(gt_classes.shape)} / valid {tuple(valid.shape)} for N={N}")
+    P = sum(h * w for h, w in hw) * A
+    slot = torch.empty((N, G), dtype=torch.int32, device=dev)
+    owner = torch.empty((N, P), dtype=torch.int32, device=dev)
+    state = torch.empty((N, P), dtype=torch.uint8, device=dev)
+    rc = _C.lib().d2mi_yolov4_assign(lhw, st, chw, L, A, N, _C.ptr(gt_boxes), _C.ptr(valid), G,
+                                     _C.ptr(slot), _C.ptr(owner), _C.stream_of(dev))
+    _C.check(rc, "d2mi_yolov4_assign")
+    conf = (geo, int(num_classes), float(image_hw[0]) * float(image_hw[1]), float(iou_threshold),
+            float(cls_normalizer), float(iou_normalizer))
+    out = _YoloLossFn.apply(conf, gt_boxes, gt_classes, valid, slot, owner, state, *logits)
+    if debug is not None:
+        debug.update(slot=slot, owner=owner, state=state)
+    return out

@@ -1,7 +1,9 @@
 """CSPDarkNet53 backbone (lib/modeling/backbone/darknet.py:14-249).
 
 Every conv is Conv2D + BatchNorm + activation (MODEL.RESNETS.ACTIVATION,
-"mish" by default).  At inference BatchNorm folds into the weights
+"mish" by default).  Built in the training phase, the BatchNorms of the stages
+that train run on batch statistics (layers/normalization.py); otherwise, and
+in the frozen stages, BatchNorm folds into the weights
 (Conv2D.effective_params) and the convs run on the MFMA implicit-GEMM kernel;
 the 3-channel stem stays on the "auto" path.  The activation follows as one
 in-place HIP pass (layers/activation.py).  Scopes, stage widths
@@ -14,6 +16,7 @@ import torch
 
 from ...layers import BatchNorm, Conv2D, Layer, get_norm
 from ...layers import initializers as init
+from ...layers.normalization import batch_norm_arg_scope
 from ...utils.arg_scope import add_arg_scope, arg_scope
 from .build import BACKBONE_REGISTRY, Backbone
 
@@ -23,6 +26,9 @@ def darknet_arg_scope(freeze, norm, activation):
     with arg_scope([Conv2D], use_bias=False, normalizer=get_norm(norm),
                    normalizer_params={"scope": "norm"}, activation=activation, impl="auto",
                    weights_initializer=init.variance_scaling(2.0, mode="fan_out")), ExitStack() as st:
+        # a frozen stage: the inference form; a stage that trains: batch
+        # statistics in the training phase (lib/modeling/backbone/darknet.py:14-32)
+        st.enter_context(batch_norm_arg_scope(norm, freeze=freeze))
         if freeze:
             st.enter_context(arg_scope([Conv2D, BatchNorm], trainable=False))
         yield

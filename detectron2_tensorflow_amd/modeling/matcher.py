@@ -150,3 +150,9 @@ def _smallest(keys, mask, k, limit):
     vals, idx = vals[:, :k], idx[:, :k]
     take = (torch.arange(k, device=keys.device)[None, :] < limit) & (vals < 2.0)
     return sel.scatter_(1, idx, take)
+
+
+# YOLOMatcher (lib/modeling/matcher.py:176-267) lives beside the loss it serves
+# and is exported here as the reference exports it.  (Imported last: the
+# single-stage heads import Matcher from this module.)
+from .single_stage_heads.yolov4_outputs import YOLOMatcher  # noqa: E402, F401

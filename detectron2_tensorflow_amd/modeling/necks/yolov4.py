@@ -1,7 +1,8 @@
 """YOLOv4 neck: SPP + PAN (lib/modeling/necks/yolov4.py:22-291).
 
 Every conv is Conv2D + MODEL.NECK.NORM + MODEL.NECK.ACTIVATION (leaky ReLU,
-alpha 0.1) on the MFMA conv kernel with the BatchNorm folded at inference.
+alpha 0.1) on the MFMA conv kernel with the BatchNorm folded at inference;
+built in the training phase the BatchNorms run on batch statistics.
 The SPP block's three stride-1 max pools and their concat are one HIP launch
 (d2mi_spp_pool) on GPU tensors that need no gradient, the MaxPool2D
 composition otherwise.  Concat orders are the reference's: SPP [pool13,
@@ -13,6 +14,7 @@ import torch
 
 from ...layers import Conv2D, Layer, MaxPool2D, ShapeSpec, Upsample, get_norm, ops
 from ...layers import initializers as init
+from ...layers.normalization import batch_norm_arg_scope
 from ...utils.arg_scope import add_arg_scope, arg_scope
 from .build import NECK_REGISTRY
 from .fpn import assert_strides_are_log2_contiguous
@@ -98,7 +100,8 @@ class YOLOV4(Layer):
         c = self.out_channels
         with arg_scope([Conv2D], use_bias=self.norm == "", normalizer=get_norm(self.norm),
                        normalizer_params={"scope": "norm"}, activation=self.activation,
-                       impl="auto", weights_initializer=init.variance_scaling(1.0)):
+                       impl="auto", weights_initializer=init.variance_scaling(1.0)), \
+                batch_norm_arg_scope(self.norm):  # (BN / SyncBN: training = the phase, no sync)
             self.process1 = SPP(self.in_channels[2], c * 4, scope="process1")
             self.process2 = TopDown(self.in_channels[1], c * 2, scope="process2")
             self.process3 = TopDown(self.in_channels[0], c, scope="process3")

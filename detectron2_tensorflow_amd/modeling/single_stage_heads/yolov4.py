@@ -1,5 +1,5 @@
 """YOLOV4Head (lib/modeling/single_stage_heads/yolov4.py:22-170,
-yolov4_outputs.py:208-264, :331-390).  Inference only.
+yolov4_outputs.py:59-390).
 
 Tower: per level a 3x3 conv (MODEL.YOLOV4.NORM / ACTIVATION) to CONV_DIMS *
 2^i and a 1x1 ``pred`` conv (bias, no norm, no activation) to A * (K + 5), on
@@ -7,19 +7,25 @@ the MFMA conv kernel.  Inference is one fused op, d2mi_yolov4_inference: the
 max-class score of every prediction, the threshold, the decode of the
 survivors, class-agnostic NMS and the padding to DETECTIONS_PER_IMAGE.
 
-Training is not implemented: the reference's loss (yolov4_outputs.py:266-329)
-needs training-mode batch statistics in the neck and head (NORM "BN":
-layers.BatchNorm has that form, but these builders build the inference form),
-YOLOMatcher and a CIoU loss.
+Training (a head built in the training phase, ``finalize(cfg, True, ...)``):
+the tower's BatchNorms run on batch statistics and ``call`` returns the
+reference's conf / cls / box losses (yolov4_outputs.py:266-329) from
+yolov4_outputs.yolov4_losses -- the fused target assignment and CIoU loss of
+csrc/yolo_loss.hip, or the tensor formulation.  The form is fixed when the
+head is built: a head built in the inference phase has
+neither and refuses ``.train()``.
 """
 import torch
 
 from ...layers import Conv2D, Layer, get_norm, ops
 from ...layers import initializers as init
+from ...layers.normalization import batch_norm_arg_scope, norm_phase
 from ...structures import BoxList
 from ...utils.arg_scope import arg_scope
 from ..anchor_generator import build_anchor_generator
+from . import yolov4_outputs
 from .build import SINGLE_STAGE_HEADS_REGISTRY
+from .yolov4_outputs import YOLOMatcher
 
 
 class YOLOV4Tower(Layer):
@@ -35,7 +41,8 @@ class YOLOV4Tower(Layer):
         with arg_scope([Conv2D], stride=1, normalizer=normalizer,
                        normalizer_params={"scope": "norm"}, use_bias=not normalizer,
                        activation=cfg.MODEL.YOLOV4.ACTIVATION, padding="SAME", impl="auto",
-                       weights_initializer=init.random_normal(0.01)):
+                       weights_initializer=init.random_normal(0.01)), \
+                batch_norm_arg_scope(cfg.MODEL.YOLOV4.NORM):  # (training = the phase, no sync)
             for i in range(3):
                 head_dims = 2 ** i * conv_dims
                 convs.append(Conv2D(in_channels[i], head_dims, 3, scope=f"conv{i + 1}"))
@@ -67,15 +74,40 @@ class YOLOV4Head(Layer):
         self.nms_threshold = y.NMS_THRESH_TEST
         self.max_detections_per_image = cfg.TEST.DETECTIONS_PER_IMAGE
         self.scale_yx = list(y.SCALE_YX)
+        # the form is fixed here, by the phase batch_norm_arg_scope read for the
+        # tower above, never by .training
+        self.built_for_training = bool(norm_phase())
+        self.matcher = None
+        if self.built_for_training:
+            self.matcher = YOLOMatcher(cfg.MODEL.SINGLE_STAGE_HEAD.IOU_THRESHOLDS[0])
 
     def call(self, images, features, targets=None):
-        if self.training:
+        if self.training and not self.built_for_training:
             raise NotImplementedError(
-                "YOLOv4 training is not implemented: the reference's loss needs training-mode "
-                "batch statistics in the neck and head (NORM \"BN\"), YOLOMatcher and a CIoU "
-                "loss; this head runs inference only")
+                "this YOLOV4Head was built in the inference phase: its BatchNorms do not run on "
+                "batch statistics and neither the YOLOMatcher nor the CIoU loss was constructed; "
+                "build the model with finalize(cfg, True, ...) to train")
         pred_logits = self.head([features[f] for f in self.in_features])
+        if self.training:
+            if targets is None:
+                raise ValueError("YOLOv4 training needs targets")
+            return None, self.losses(images, pred_logits, targets)
         return self.inference(pred_logits), {}
+
+    def losses(self, images, pred_logits, gt):
+        """YOLOV4Outputs.losses (yolov4_outputs.py:266-329).  The GT that count
+        are is_valid & ~crowd & ~difficult (:80); the box weight's area is the
+        padded batch tensor's (:46, :301)."""
+        valid = gt["is_valid"].bool()
+        for k in ("gt_is_crowd", "gt_difficult"):
+            if gt.get(k) is not None:
+                valid = valid & ~gt[k].bool()
+        image_hw = tuple(images.tensor.shape[1:3])
+        conf, cls, box, _, _ = yolov4_outputs.yolov4_losses(
+            pred_logits, self.anchor_generator.strides, self.anchor_generator.cell_anchors,
+            self.scale_yx, self.num_classes, gt["gt_boxes"], gt["gt_classes"], valid, image_hw,
+            self.matcher.threshold, self.cls_normalizer, self.iou_normalizer)
+        return {"conf_loss": conf, "cls_loss": cls, "box_loss": box}
 
     def inference(self, pred_logits):
         ob, os_, oc, ov = ops.yolov4_inference(

@@ -426,6 +426,61 @@ int d2mi_spp_pool(const float* x, int N, int H, int W, int C, float* out, void* 
  * (:5-7). */
 int d2mi_activation(float* x, int64_t n, int code, float alpha, void* stream);
 
+/* -------------------------------------------------------- YOLOv4 training
+ * The host arrays, the logits layout and the prediction order of the YOLOv4
+ * section above; L = 3, any K >= 1, any G >= 0.  Device arrays: gt_boxes
+ * [N, G, 4] yxyx (16-byte aligned), gt_classes [N, G] int64, valid [N, G]
+ * bytes = is_valid & ~crowd & ~difficult (yolov4_outputs.py:77-80).
+ *
+ * YOLOV4Outputs._get_ground_truth's assignment (yolov4_outputs.py:86-146,
+ * YOLOMatcher's argmax, matcher.py:233) and the slot collisions of its
+ * sparse.to_dense scatters (:155-196): for every valid GT the first maximum
+ * of the L * A plain IoUs of [0, 0, h / stride_l, w / stride_l] against level
+ * l's cell anchors in pixels, level = best / A, anchor = best % A, cell =
+ * floor(centre / stride_level).  slot [N, G]: the flat prediction index, -1
+ * for a GT that is not valid or whose cell is outside the grid.  owner
+ * [N, P]: the highest GT index whose slot the prediction is (the target box
+ * the scatter leaves), -1 where none.  Two launches (owner's clear, the
+ * assignment); no memset node. */
+int d2mi_yolov4_assign(const int32_t* level_hw, const float* strides, const float* cell_hw, int L,
+                       int A, int N, const float* gt_boxes, const uint8_t* valid, int G,
+                       int32_t* slot, int32_t* owner, void* stream);
+/* YOLOV4Outputs.losses (yolov4_outputs.py:266-329) before its 1 / N and
+ * CLS_NORMALIZER / N factors, with the negatives of YOLOMatcher
+ * (matcher.py:223-242: max over the valid GT of pairwise CIoU(GT, predicted
+ * box), box_list_ops.py:295-372, below iou_threshold; none in an image without
+ * a valid GT) and iou_loss "ciou" on matched_iou(prediction, GT)
+ * (loss.py:140-196, box_list_ops.py:375-450, width2 = x_max1 - x_min2 kept).
+ * partial [N * d2mi_yolov4_loss_blocks()][5] float64: per-workgroup sums (the
+ * float32 terms added in float64) of
+ *   0  (respond_bbox - sigmoid(conf))^2 * BCE(conf) over positives and negatives
+ *   1  BCE(class logits, multi-hot of the slot's GT classes) over positives
+ *   2  (2 - gt_area / image_area) * iou_normalizer / N * (1 - ciou) over positives
+ *   3, 4  the positives and the negatives counted
+ * to be added in a fixed order by the caller.  state [N, P] bytes: 0 neither,
+ * 1 negative, 2 positive.  One launch. */
+int d2mi_yolov4_loss_blocks(void);
+int d2mi_yolov4_loss_fwd(const float* const* logits, const int32_t* level_hw, const float* strides,
+                         const float* cell_hw, const float* scale_yx, int L, int A, int K, int N,
+                         const float* gt_boxes, const int64_t* gt_classes, const uint8_t* valid,
+                         int G, const int32_t* slot, const int32_t* owner, float image_area,
+                         float iou_threshold, float iou_normalizer, double* partial,
+                         uint8_t* state, void* stream);
+/* The gradient of conf_scale * sum 0, cls_scale * sum 1 and sum 2 above with
+ * respect to every logit, times the upstream gradients *g_conf, *g_cls, *g_box
+ * (device scalars; null = 0): what TF differentiates, the focal factor, alpha
+ * and v of the CIoU, width2 and the decode included; nothing through the
+ * targets.  EVERY element of every d_logits[l] is written (zeros where the
+ * loss does not reach).  One launch, no float atomics. */
+int d2mi_yolov4_loss_bwd(const float* const* logits, float* const* d_logits,
+                         const int32_t* level_hw, const float* strides, const float* cell_hw,
+                         const float* scale_yx, int L, int A, int K, int N, const float* gt_boxes,
+                         const int64_t* gt_classes, int G, const int32_t* slot,
+                         const int32_t* owner, const uint8_t* state, float image_area,
+                         float iou_normalizer, float conf_scale, float cls_scale,
+                         const float* g_conf, const float* g_cls, const float* g_box,
+                         void* stream);
+
 /* ------------------------------------------------------------ Matrix NMS
  * lib/layers/nms.py:29-83 (SOLOv2 Matrix-NMS).  masks [M, HW] float,
  * classes int64 [M], scores [M], sum_masks [M] (nullable: computed);
