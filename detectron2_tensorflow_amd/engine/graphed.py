@@ -70,7 +70,7 @@ import os
 
 import torch
 
-from ..layers import convolutional
+from ..layers import conv_grad
 from ..modeling.roi_heads.roi_heads import DeferredMaskLoss, ROIHeads, StandardROIHeads
 from ..utils import capture, host_sync
 from .trainer import Trainer
@@ -168,7 +168,7 @@ class GraphedTrainer(Trainer):
         self.enabled = next(model.parameters()).is_cuda
         self._U = None
         # r6: capture the backward with every conv's weight gradient on a side
-        # stream (layers/convolutional.py WGRAD_STREAM).  Off by default:
+        # stream (layers/conv_grad.py wgrad_on).  Off by default:
         # bit-identical, but no faster -- 105.3 / 105.8 vs 105.6 / 106.1 img/s
         # in alternating bench runs (profiles/r6l_bench_wgrad_side_ab.txt): the
         # warp-specialised convs hold a whole CU each, so the branches contend
@@ -338,14 +338,10 @@ class GraphedTrainer(Trainer):
                 self.reducer.begin_capture()
             # the convs' weight gradients on a side stream beside their data
             # gradients: forked branches of the captured graph (r6)
-            if self.wgrad_side:
-                if self._wgrad_stream is None:
-                    self._wgrad_stream = torch.cuda.Stream(device=dev)
-                convolutional.WGRAD_STREAM["stream"] = self._wgrad_stream
-            try:
+            if self.wgrad_side and self._wgrad_stream is None:
+                self._wgrad_stream = torch.cuda.Stream(device=dev)
+            with conv_grad.wgrad_on(self._wgrad_stream):  # (None: on this stream)
                 total.backward(seed, retain_graph=True)
-            finally:
-                convolutional.WGRAD_STREAM.pop("stream", None)
             self.reducer.finish()
             events = self.reducer.end_capture() if dp else None
             if not dp:

@@ -5,7 +5,7 @@ so that the receiver adds it inside its own kernel epilogue: no autograd add of
 two full maps, no separate ReLU-backward pass, no zero-fill of pooled levels.
 This module holds the state machines of those hand-offs (torch only: it runs
 on a CPU-only machine); the kernels are launched by their callers
-(layers/convolutional.py:_ConvMFMAFn, layers/ops/roi.py:_RoIAlignFn,
+(layers/conv_grad.py:_ConvMFMAFn, layers/ops/roi.py:_RoIAlignFn,
 modeling/proposal_generator/rpn.py:_RPNHead1x1Fn).
 
 ``ReluTag`` -- fused-ReLU chains.  A conv with a fused ReLU tags its output.  A

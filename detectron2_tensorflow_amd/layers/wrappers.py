@@ -7,6 +7,7 @@ from . import initializers as init
 from . import ops
 from .activation import get_activation
 from .base import Layer
+from .conv_weights import Versioned, version_key
 from .convolutional import fix_padding
 from .functional import upsample
 
@@ -96,14 +97,12 @@ class Linear(Layer):
         if normalizer is not None:
             self.normalizer_fn = normalizer(**(normalizer_params or {}))
         self.act_fn = get_activation(activation)
+        self._pack = Versioned()
 
     def _packed(self):
-        key = (self.weights.data_ptr(), self.weights._version)
-        if getattr(self, "_pk_key", None) != key:
-            K, N = self.weights.shape
-            self._pk = ops.pack_conv_weights(self.weights.detach().reshape(1, 1, K, N))
-            self._pk_key = key
-        return self._pk
+        w = self.weights
+        return self._pack.get(version_key((w,)),
+                              lambda: ops.pack_conv_weights(w.detach().reshape(1, 1, *w.shape)))
 
     def call(self, inputs):
         x = inputs.reshape(inputs.shape[0], -1) if inputs.dim() > 2 else inputs

@@ -1,6 +1,6 @@
 """BACKBONE_REGISTRY / build_backbone (lib/modeling/backbone/build.py)."""
 from ...layers import Layer, ShapeSpec
-from ...layers.convolutional import FoldGroup
+from ...layers.conv_weights import FoldGroup
 from ...utils.registry import Registry
 
 BACKBONE_REGISTRY = Registry("BACKBONE")

@@ -1,5 +1,5 @@
 """META_ARCH_REGISTRY / build_model (lib/modeling/meta_arch/build.py:3-16)."""
-from ...layers.convolutional import PackGroup
+from ...layers.conv_weights import PackGroup
 from ...utils.registry import Registry
 
 META_ARCH_REGISTRY = Registry("META_ARCH")

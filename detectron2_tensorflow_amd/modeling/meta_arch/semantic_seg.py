@@ -34,7 +34,8 @@ import torch
 from ...layers import Conv2D, GroupNorm, Layer, Sequential, Upsample
 from ...layers import initializers as init
 from ...layers import ops
-from ...layers.convolutional import _conv_mfma
+from ...layers.conv_weights import Versioned
+from ...layers.convolutional import conv_padded_out
 from ...utils.arg_scope import arg_scope
 from ...utils.registry import Registry
 from ..backbone import build_backbone
@@ -87,8 +88,7 @@ class SemSegFPNHead(Layer):
         # constant zero columns for the MFMA predictor (not variables)
         self.register_buffer("_pred_pad_w", torch.zeros(1, 1, dims, padc), persistent=False)
         self.register_buffer("_pred_pad_b", torch.zeros(padc), persistent=False)
-        self._pred_packed = None
-        self._pred_packed_key = None
+        self._pred_pack = Versioned()
 
     def _merged(self, features):
         """The sum of the scale heads (semantic_seg.py:191-195)."""
@@ -113,15 +113,8 @@ class SemSegFPNHead(Layer):
     def _predict(self, x):
         """[N, h, w, ldc] logits, ldc = NUM_CLASSES padded to a multiple of 4."""
         p = self.predictor
-        w, b = p.weights, p.bias
-        if self._pred_pad_b.numel():
-            w = torch.cat([w, self._pred_pad_w], 3)
-            b = torch.cat([b, self._pred_pad_b])
-        key = (p.weights.data_ptr(), p.weights._version)
-        if self._pred_packed is None or self._pred_packed_key != key:
-            self._pred_packed = ops.pack_conv_weights(w.detach())
-            self._pred_packed_key = key
-        return _conv_mfma(x, w, b, self._pred_packed, 1, (0, 0), relu=False)
+        return conv_padded_out(x, p.weights, p.bias, self._pred_pad_w, self._pred_pad_b,
+                               self._pred_pack, 1, (0, 0))
 
     def call(self, features, targets=None, image_shapes=None):
         """(logits [N, h, w, ldc] at COMMON_STRIDE, losses).  targets

@@ -9,6 +9,7 @@ level NMS, per-image top-k(post) and padding — in one fixed launch sequence.
 import torch
 
 from ...layers import Conv2D, Layer
+from ...layers.conv_weights import Versioned, version_key
 from ...layers.convolutional import same_pads
 from ...layers import initializers as init
 from ...layers import handoff, ops
@@ -35,7 +36,7 @@ class StandardRPNHead(Layer):
     CONCAT_OUT = True
     # True: the shared 3x3's weight / bias gradient accumulates over the FPN
     # levels in one buffer (the MFMA wgrad's reduce adds each level into it;
-    # layers/convolutional.py:_wgrad_shared) -- autograd's per-level adds go
+    # layers/conv_grad.py:_weight_grad) -- autograd's per-level adds go
     ACC_CONV_LEVELS = True
     # True: the head hands a handoff.RowBound from the loss to its backwards.
     # When RPN.losses declares the sampled anchors per image on it, the levels
@@ -61,9 +62,8 @@ class StandardRPNHead(Layer):
         self.objectness_logits = Conv2D(in_channels, self.A, 1, stride=1, scope="objectness_logits")
         self.anchor_deltas = Conv2D(in_channels, self.A * self.box_dim, 1, stride=1,
                                     scope="anchor_deltas")
-        self._fused = None
-        self._fused_key = None
-        self._fused_pad = None
+        self._fused = Versioned()
+        self._fused_pad = Versioned()
 
     def _fused_1x1(self):
         """The objectness (A) and anchor-delta (4A) 1x1 convs as ONE conv of
@@ -73,20 +73,17 @@ class StandardRPNHead(Layer):
         named for the FPN width)."""
         wo, wd = self.objectness_logits.weights, self.anchor_deltas.weights
         bo, bd = self.objectness_logits.bias, self.anchor_deltas.bias
-        key = (wo._version, wd._version, bo._version, bd._version, wo.data_ptr(), wd.data_ptr())
-        if self._fused is None or self._fused_key != key:
+        def fuse():
             n = wo.shape[3] + wd.shape[3]
             pad = (-n) % 4
-            zp = self._fused_pad
-            if zp is None or zp[0].shape[:3] != wo.shape[:3] or zp[0].shape[3] != pad \
-                    or zp[0].device != wo.device:
-                # the zero pad columns, made once (not two fills per step)
-                zp = self._fused_pad = (wo.new_zeros(*wo.shape[:3], pad), bo.new_zeros(pad))
+            # the zero pad columns, made once (not two fills per step)
+            zp = self._fused_pad.get((wo.shape, pad, wo.device), lambda: (
+                wo.new_zeros(*wo.shape[:3], pad), bo.new_zeros(pad)))
             w = torch.cat([wo.detach(), wd.detach(), zp[0]], dim=3)
             b = torch.cat([bo.detach(), bd.detach(), zp[1]])
-            self._fused = (w.contiguous(), ops.pack_conv_weights(w), b.contiguous())
-            self._fused_key = key
-        return self._fused
+            return w.contiguous(), ops.pack_conv_weights(w), b.contiguous()
+
+        return self._fused.get(version_key((wo, wd, bo, bd)), fuse)
 
     def call(self, features):
         rpn_features, logits, deltas = [], [], []
@@ -198,7 +195,7 @@ class _RPNHead1x1Fn(torch.autograd.Function):
     16 output columns, at most 80 columns) sliced per head.  The
     input gradient leaves through the dgrad's ReLU gate (share > 0) when share
     is a fused-ReLU conv output, which then skips its threshold_backward (the
-    sole-consumer protocol of layers/convolutional.py:_ConvMFMAFn)."""
+    sole-consumer protocol of layers/conv_grad.py:_ConvMFMAFn)."""
     GATE = True  # False: leave the ReLU backward to the 3x3 conv (tests)
     # True: the levels of one forward share a weight-gradient accumulator
     # (wacc: a handoff.LevelAccumulator); every level but the last returns no

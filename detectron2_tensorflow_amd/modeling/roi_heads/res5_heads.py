@@ -47,7 +47,7 @@ class Res5ROIHeads(StandardROIHeads):
 
     def _init_box_head(self, cfg):
         from ..backbone.resnet import BottleneckBlock, Stage, resnet_arg_scope
-        from ...layers.convolutional import FoldGroup
+        from ...layers.conv_weights import FoldGroup
         assert len(self.in_features) == 1
         b, r = cfg.MODEL.ROI_BOX_HEAD, cfg.MODEL.RESNETS
         res = b.POOLER_RESOLUTION

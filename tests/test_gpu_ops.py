@@ -916,7 +916,8 @@ def test_conv2d_residual_relu_after_and_split_k(dev, shape):
 def test_conv_mfma_autograd_matches_torch(dev, conf):
     """Gradients of the MFMA conv layer (x, w, b, top-down, residual) vs
     autograd of the fp64 torch reference."""
-    from detectron2_tensorflow_amd.layers.convolutional import _ConvMFMAFn, same_pads
+    from detectron2_tensorflow_amd.layers.conv_grad import _ConvMFMAFn
+    from detectron2_tensorflow_amd.layers.convolutional import same_pads
     N, H, W, Cin, Cout, k, stride, relu, td, res = conf
     g = torch.Generator().manual_seed(sum(conf[:7]))
     x = torch.randn(N, H, W, Cin, generator=g)
@@ -1163,7 +1164,7 @@ def test_relu_gate_fused_into_consumer_dgrad(dev, declared):
     dgrad epilogue (kMaskByResidual) and the producer skips its own; without
     the declaration nothing is fused.  Gradients match float64 autograd."""
     from detectron2_tensorflow_amd.layers import handoff
-    from detectron2_tensorflow_amd.layers.convolutional import _ConvMFMAFn
+    from detectron2_tensorflow_amd.layers.conv_grad import _ConvMFMAFn
     g = torch.Generator().manual_seed(11)
     x = torch.randn(2, 12, 15, 64, generator=g)
     ws = [torch.randn(3, 3, 64, 64, generator=g) / 24 for _ in range(3)]
@@ -1588,7 +1589,7 @@ def test_pack_weights_many_and_pack_group(dev):
     launches; other Cin alone), and a PackGroup repacks every member whose
     parameters changed in one call, leaving the fresh ones untouched."""
     from detectron2_tensorflow_amd.layers import Conv2D
-    from detectron2_tensorflow_amd.layers.convolutional import PackGroup
+    from detectron2_tensorflow_amd.layers.conv_weights import PackGroup
     g = torch.Generator().manual_seed(21)
     shapes = [(3, 3, 256, 256), (1, 1, 512, 256), (1, 1, 24, 16), (3, 3, 64, 100)] * 9
     ws = [torch.randn(*s, generator=g).to(dev) for s in shapes]
@@ -1603,7 +1604,7 @@ def test_pack_weights_many_and_pack_group(dev):
     for c in convs:
         c(x)
     assert len(grp.members) == 3
-    kept = convs[2]._packed
+    kept = convs[2]._pack.value
     with torch.no_grad():
         convs[0].weights.add_(1.0)
         convs[1].weights.mul_(0.5)
@@ -1616,9 +1617,9 @@ def test_pack_weights_many_and_pack_group(dev):
     finally:
         ops().pack_conv_weights_many = real
     assert calls == [2]
-    assert convs[2]._packed is kept
+    assert convs[2]._pack.value is kept
     for c in convs:
-        assert torch.equal(c._packed, ops().pack_conv_weights(c.weights.detach()))
+        assert torch.equal(c._pack.value, ops().pack_conv_weights(c.weights.detach()))
 
 
 @pytest.mark.parametrize("shape", [(2, 64, 96), (1, 37, 53), (2, 800, 1344)])

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from detectron2_tensorflow_amd.layers import handoff as H
+from detectron2_tensorflow_amd.layers.conv_grad import input_grad
 from detectron2_tensorflow_amd.layers.handoff import (DeferredPixels, HandoffError,
                                                       LevelAccumulator, Links, Pair, PoolerShare,
                                                       ReluTag, Slot)
@@ -41,11 +42,15 @@ def in_backward(*fns):
 
 
 def conv_backward(links, gx, gate_ok=True):
-    """_ConvMFMAFn.backward's input-gradient part with the dgrad stood in:
+    """_ConvMFMAFn.backward's input-gradient step with the dgrad stood in:
     (what the backward returns for x, what the dgrad was asked for)."""
-    plan = links.plan(gate_ok)
-    asked = {"add": plan.add, "add2": plan.add2, "gate": plan.gate}
-    return plan.finish(gx), asked
+    asked = {}
+
+    def dgrad(gate, add, add2):
+        asked.update(add=add, add2=add2, gate=gate)
+        return gx
+
+    return input_grad(links, gate_ok, dgrad), asked
 
 
 def bound(links, x=None, topdown=None, has_residual=False):

@@ -23,7 +23,7 @@ def _fpn_join(on):
 
 
 def _pack_group(on):
-    from detectron2_tensorflow_amd.layers.convolutional import PackGroup
+    from detectron2_tensorflow_amd.layers.conv_weights import PackGroup
     PackGroup.ENABLED = on
 
 
