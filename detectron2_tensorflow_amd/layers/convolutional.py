@@ -33,11 +33,13 @@ def epilogue(y, norm, act_fn, *, allow_fused_gn, fused_relu=False, final_relu=Fa
     """What follows a conv (+ bias): the normalizer, then the activation and
     final_relu (the ReLU of a layer without one) unless the conv fused them
     (fused_relu).  allow_fused_gn: GroupNorm + ReLU as one HIP pass where the
-    normalizer can (fused_ok); only Conv2D's MFMA sites take it."""
+    normalizer can (fused_ok, or train_fused_ok where it has one: the training
+    kernels); only Conv2D's MFMA sites take it."""
     if final_relu and act_fn is not None:
         raise ValueError("final_relu is for layers without an activation")
     if norm is not None:
-        if allow_fused_gn and is_relu(act_fn) and hasattr(norm, "fused_ok") and norm.fused_ok(y):
+        if allow_fused_gn and is_relu(act_fn) and hasattr(norm, "fused_ok") and (
+                norm.fused_ok(y) or (hasattr(norm, "train_fused_ok") and norm.train_fused_ok(y))):
             return norm(y, relu=True)
         y = norm(y)
     if act_fn is not None and not fused_relu:

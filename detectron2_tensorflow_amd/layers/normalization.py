@@ -94,23 +94,30 @@ class GroupNorm(Layer):
         affine parameters require one (a frozen GN in a trainable branch must
         still pass the input gradient through torch's group_norm)."""
         C = self.channels
-        needs_grad = torch.is_grad_enabled() and (
-            x.requires_grad or self.gamma.requires_grad or self.beta.requires_grad)
-        return (x.is_cuda and not needs_grad
+        return (x.is_cuda and not self._needs_grad(x)
                 and C % self.num_groups == 0 and (C // self.num_groups) % 4 == 0 and C <= 1024
                 and self.num_groups <= 64)
+
+    def _needs_grad(self, x):
+        return torch.is_grad_enabled() and (
+            x.requires_grad or self.gamma.requires_grad or self.beta.requires_grad)
+
+    def train_fused_ok(self, x):
+        """A call that needs a gradient runs the HIP training kernels
+        (ops.group_norm_train's fused arm), ReLU included."""
+        return self._needs_grad(x) and ops.gn_train_fused(x, self.channels, self.num_groups)
 
     def call(self, x, relu=False, up2=False, accumulate_into=None):
         """GroupNorm.call (normalization.py:235-260) on NHWC.  relu / up2 /
         accumulate_into fuse the ops that follow it in the SOLOv2 heads (HIP
-        path); training (autograd) runs on torch's group_norm."""
+        inference path); a call that needs a gradient runs
+        ops.group_norm_train (GroupNorm + ReLU), then up2 / the sum."""
         if self.fused_ok(x):
             return ops.group_norm(x, self.num_groups, self.gamma, self.beta, self.epsilon,
                                   relu, up2, accumulate_into)
-        y = torch.nn.functional.group_norm(x.permute(0, 3, 1, 2), self.num_groups, self.gamma,
-                                           self.beta, self.epsilon).permute(0, 2, 3, 1)
-        if relu:
-            y = torch.relu(y)
+        # (without a gradient and outside fused_ok -- the CPU, C > 1024 -- torch, as ever)
+        norm = ops.group_norm_train if self._needs_grad(x) else ops.norm.group_norm_torch
+        y = norm(x, self.num_groups, self.gamma, self.beta, self.epsilon, relu)
         if up2:
             y = y.repeat_interleave(2, 1).repeat_interleave(2, 2)
         if accumulate_into is not None:

@@ -9,8 +9,8 @@ One module per kernel family, cut as csrc/ is; this
 package re-exports their public functions, classes and constants.  The
 process-wide toggles are not re-exported: each is an attribute of the one
 module that owns it (roi.MERGED_BWD, roi.DEFER_PIXELS, conv.CONV_MATH,
-relation.FUSED_RELATION, res5.FUSED_POOL, norm.FUSED_BN_TRAIN), read and
-written there.
+relation.FUSED_RELATION, res5.FUSED_POOL, norm.FUSED_BN_TRAIN,
+norm.FUSED_GN_TRAIN), read and written there.
 """
 from ._common import (BOX_MODE_ALIGNED, BOX_MODE_RAW, BOX_MODE_UNALIGNED, get_tuning,  # noqa: F401
                       set_tuning)
@@ -34,8 +34,8 @@ from .detect import (ACT_LEAKY_RELU, ACT_MISH, activation_, fast_rcnn_inference,
 from .fold import fold_frozen_bn, fold_frozen_bn_many  # noqa: F401
 from .losses import (fast_rcnn_loss, mask_loss, retina_loss, rpn_loss,  # noqa: F401
                      scale_gradient, yolov4_loss)
-from .norm import (batch_norm_train, group_norm, group_norm_levels, resize_bilinear,  # noqa: F401
-                   resize_bilinear_grad)
+from .norm import (batch_norm_train, gn_train_fused, group_norm, group_norm_levels,  # noqa: F401
+                   group_norm_train, resize_bilinear, resize_bilinear_grad)
 from .relation import relation_attention, relation_supported  # noqa: F401
 from .res5 import res5_pool, res5_pool_dense  # noqa: F401
 from .roi import DeferredPixels, roi_align, roi_touched_rows  # noqa: F401

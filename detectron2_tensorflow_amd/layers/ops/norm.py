@@ -1,6 +1,6 @@
 """GroupNorm, BatchNorm on batch statistics and bilinear resize on NHWC
 (csrc/group_norm.hip, csrc/batch_norm.hip; the resize kernel lives in
-solo.hip).  Owns the FUSED_BN_TRAIN toggle."""
+solo.hip).  Owns the FUSED_BN_TRAIN and FUSED_GN_TRAIN toggles."""
 import torch
 import torch.distributed as dist
 
@@ -63,6 +63,119 @@ def group_norm_levels(xs, num_groups, gamma, beta, eps, relu=False):
                                          _C.ptr(ws), wsb, _C.stream_of(xs[0].device))
     _C.check(rc, "d2mi_group_norm_nhwc_levels")
     return ys
+
+
+# ------------------------------------------------------ GroupNorm, training
+# True: a GroupNorm that needs a gradient runs d2mi_group_norm_train_fwd /
+# _bwd on a GPU float32 tensor whose sizes those kernels take; False: torch's
+# group_norm on the permuted (NCHW) view, then torch.relu (the arm that also
+# serves CPU tensors and refused sizes).  Tests and tools/gn_train_ab.py
+# compare the two; DESIGN section 5 has the measurements behind the default.
+FUSED_GN_TRAIN = True
+
+# whether the kernels take (N, C, G): what the C entries' own size check says
+# (a workspace query answers 0 for sizes they refuse), asked once per triple
+_GN_SIZES = {}
+
+
+def _gn_sizes_ok(N, C, G):
+    key = (N, C, G)
+    ok = _GN_SIZES.get(key)
+    if ok is None:
+        ok = _GN_SIZES[key] = _C.lib().d2mi_group_norm_train_bwd_workspace_size(
+            max(N, 1), 1, 1, C, G) > 0
+    return ok
+
+
+def gn_train_fused(x, C, G):
+    """Whether ops.group_norm_train runs the HIP kernels for x [N, H, W, C]
+    with G groups: the toggle, a GPU float32 tensor, and sizes the kernels
+    take (C / G a multiple of 4, C <= 2048, G <= 64)."""
+    return (FUSED_GN_TRAIN and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and _gn_sizes_ok(int(x.shape[0]), int(C), int(G)))
+
+
+def group_norm_torch(x, num_groups, gamma, beta, eps, relu=False):
+    """GroupNorm (+ ReLU) of NHWC x on torch's group_norm over the permuted
+    (NCHW) view: the arm of CPU tensors, refused sizes and the toggle off."""
+    y = torch.nn.functional.group_norm(x.permute(0, 3, 1, 2), num_groups, gamma, beta,
+                                       eps).permute(0, 2, 3, 1)
+    if relu:
+        y = torch.relu(y)
+    return y
+
+
+# workspace bytes per (entry, N, H, W, C, G): pure functions of the shape
+_GN_WS = {}
+
+
+def _gn_workspace(query, shape, G, device):
+    key = (query,) + tuple(shape) + (G,)
+    wsb = _GN_WS.get(key)
+    if wsb is None:
+        wsb = _GN_WS[key] = getattr(_C.lib(), query)(*shape, G)
+    return _C.scratch(wsb, device), wsb
+
+
+class _GroupNormTrainFn(torch.autograd.Function):
+    """GroupNorm (+ ReLU) on NHWC with the explicit backward of
+    d2mi_group_norm_train_bwd.  Saves x, mean, var, gamma and beta; the
+    backward recomputes the ReLU's mask from them."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, G, eps, relu):
+        xc = _f32c(x.detach())
+        g, b = _f32c(gamma.detach()), _f32c(beta.detach())
+        _C.require_device(xc, g, b)
+        N, H, W, C = xc.shape
+        y = torch.empty_like(xc)
+        mean, var = torch.empty((2, N, G), dtype=torch.float32, device=xc.device).unbind(0)
+        if N:
+            ws, wsb = _gn_workspace("d2mi_group_norm_train_fwd_workspace_size", xc.shape, G,
+                                    xc.device)
+            # x three times (two moment passes, the apply), y once
+            _bn_timed("gn_train_fwd", 16.0 * xc.numel(),
+                      lambda: _C.lib().d2mi_group_norm_train_fwd(
+                          _C.ptr(xc), N, H, W, C, G, _C.ptr(g), _C.ptr(b), eps, relu, _C.ptr(y),
+                          _C.ptr(mean), _C.ptr(var), _C.ptr(ws), wsb, _C.stream_of(xc.device)))
+        ctx.save_for_backward(xc, mean, var, g, b)
+        ctx.conf = (G, eps, relu)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xc, mean, var, g, b = ctx.saved_tensors
+        G, eps, relu = ctx.conf
+        N, H, W, C = xc.shape
+        want_x, want_g, want_b = ctx.needs_input_grad[:3]
+        if N == 0:  # nothing to launch: an empty dx, zero sums
+            return (torch.empty_like(xc) if want_x else None,
+                    torch.zeros_like(g) if want_g else None,
+                    torch.zeros_like(b) if want_b else None, None, None, None)
+        dyc = _f32c(dy)
+        dx = torch.empty_like(xc) if want_x else None
+        dgamma = torch.empty_like(g) if want_g else None
+        dbeta = torch.empty_like(b) if want_b else None
+        ws, wsb = _gn_workspace("d2mi_group_norm_train_bwd_workspace_size", xc.shape, G, xc.device)
+        # the reduce pass reads x and dy; the apply pass reads both again and writes dx
+        nbytes = 4.0 * xc.numel() * (2 + (3 if want_x else 0))
+        _bn_timed("gn_train_bwd", nbytes,
+                  lambda: _C.lib().d2mi_group_norm_train_bwd(
+                      _C.ptr(xc), _C.ptr(dyc), N, H, W, C, G, _C.ptr(mean), _C.ptr(var), _C.ptr(g),
+                      _C.ptr(b), eps, relu, _C.ptr(dx), _C.ptr(dgamma), _C.ptr(dbeta), _C.ptr(ws),
+                      wsb, _C.stream_of(xc.device)))
+        return dx, dgamma, dbeta, None, None, None
+
+
+def group_norm_train(x, num_groups, gamma, beta, eps, relu=False):
+    """GroupNorm (+ ReLU) of x [N, H, W, C] that autograd can differentiate
+    (lib/layers/normalization.py:174-260).  Where gn_train_fused holds: the
+    HIP kernels (y has ops.group_norm's bits); else torch's group_norm on the
+    NCHW view, then torch.relu."""
+    G = int(num_groups)
+    if gn_train_fused(x, x.shape[-1], G):
+        return _GroupNormTrainFn.apply(x, gamma, beta, G, float(eps), int(bool(relu)))
+    return group_norm_torch(x, G, gamma, beta, eps, relu)
 
 
 # ------------------------------------------- BatchNorm on batch statistics

@@ -86,7 +86,10 @@ class GeneralizedRCNN(_Preprocess, Layer):
         shared = set(rh.in_features) & set(getattr(pg, "in_features", ()))
         for f in shared:
             t = features[f]
-            if t.is_cuda and t.requires_grad and t.shape[-1] >= 64:
+            # (the tag rides on the tensor object: the pooler reads a contiguous
+            # copy of a permuted view -- torch's group_norm arm in a GN neck --
+            # and would never see it, leaving the RPN conv's half open)
+            if t.is_cuda and t.requires_grad and t.shape[-1] >= 64 and t.is_contiguous():
                 handoff.tag(t, handoff.LEVEL_PAIR, handoff.Pair())
 
     def call(self, batched_inputs):

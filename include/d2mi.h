@@ -585,6 +585,41 @@ int d2mi_group_norm_nhwc_levels(const float* const* xs, const int32_t* dims, int
                                 int G, const float* gamma, const float* beta, float eps, int relu,
                                 float* const* ys, void* workspace, size_t workspace_bytes,
                                 void* stream);
+/* GroupNorm.call with a gradient, forward (lib/layers/normalization.py:174-260:
+ * the layer's variables, tf.nn.moments and tf.nn.batch_normalization as TF
+ * differentiates them): y [N,H,W,C] as d2mi_group_norm_nhwc writes it (the same
+ * passes and chunking: the same bits; no up2 / accumulate), and the batch
+ * moments mean / var [N, G] (biased, two-pass) to caller tensors for the
+ * backward.  C / G % 4 == 0, C <= 2048 (C / 4 > 256: the channel quads in
+ * tiles of 256), G <= 64, N <= 65535, 16-B aligned; N == 0 launches nothing.
+ * One call launches all five passes; workspace from
+ * d2mi_group_norm_train_fwd_workspace_size. */
+size_t d2mi_group_norm_train_fwd_workspace_size(int N, int H, int W, int C, int G);
+int d2mi_group_norm_train_fwd(const float* x, int N, int H, int W, int C, int G,
+                              const float* gamma, const float* beta, float eps, int relu,
+                              float* y, float* mean, float* var, void* workspace,
+                              size_t workspace_bytes, void* stream);
+/* The gradient of the above (lib/layers/normalization.py:174-260 under
+ * tf.gradients), from x, dy [N,H,W,C], the forward's mean / var and gamma /
+ * beta; no saved y.  With r = rsqrt(var + eps), xh = (x - mean) * r,
+ * m = H*W*C/G and dz = dy where the fused ReLU passed (relu: the mask is
+ * z > 0 of z recomputed by the forward's expression; else dz = dy):
+ *   dbeta_c = sum_{n,hw} dz,  dgamma_c = sum_{n,hw} dz * xh,
+ *   S1 = sum_{hw, c in g} dz * gamma_c,  S2 = sum_{hw, c in g} dz * gamma_c * xh,
+ *   dx = r * (dz * gamma_c - S1 / m - xh * S2 / m).
+ * A reduce pass (per image, pixel chunk and channel), two small finalize
+ * launches (per image: its chunks; then S1 / S2 per image and dgamma / dbeta
+ * over the images) and an apply pass, all from this one call; fixed-order sums, no
+ * atomics, every output element written.  dx [N,H,W,C], dgamma / dbeta [C]
+ * are each nullable: a null output and the pass that only serves it are
+ * skipped.  Sizes as the forward; workspace from
+ * d2mi_group_norm_train_bwd_workspace_size. */
+size_t d2mi_group_norm_train_bwd_workspace_size(int N, int H, int W, int C, int G);
+int d2mi_group_norm_train_bwd(const float* x, const float* dy, int N, int H, int W, int C, int G,
+                              const float* mean, const float* var, const float* gamma,
+                              const float* beta, float eps, int relu, float* dx, float* dgamma,
+                              float* dbeta, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 /* ------------------------------------------- BatchNorm, batch statistics
  * The training form of BatchNorm.call (lib/layers/normalization.py:97-119:
