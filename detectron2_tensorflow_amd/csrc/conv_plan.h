@@ -455,4 +455,202 @@ inline int plan_wgrad(const ConvShape& s, int flags, int operands, size_t worksp
   return 0;
 }
 
+// ---- grouped weight gradients (d2mi_conv2d_wgrad_group): many small wgrads
+// in one launch and one reduce per kernel family instead of a pair of small
+// grids each (tuning "wgrad_group" = 1, the default: every problem with the
+// pixel splits of its own plan, so with the bits of its single launch; the
+// workspace then holds all the problems' slabs at once).  Alone, a wgrad of
+// 2-72 output tiles also has to cut its pixels into 14-62 splits to fill the
+// chip by itself; under "wgrad_group" = 2 a family's tile-chunks fill it
+// together with long pixel walks and few partial slabs, at the price of
+// other rounding.
+constexpr int kMaxWgradGroup = 64;
+// A workgroup's fixed cost (prologue, epilogue, slab write) in 32-pixel chunk
+// steps: the warp-specialised kernel's share of its peak at 19, 75 and 300
+// chunks per workgroup (0.321, 0.447, 0.506) fits 0.53 n / (n + 14).
+constexpr int kWgradGroupFixed = 14;
+enum WgradFamily {
+  kWgradFamWS = 0,       // conv_wgrad_ws_kernel<1>
+  kWgradFamWSInc = 1,    // conv_wgrad_ws_kernel<1, true>
+  kWgradFamSplit22 = 2,  // conv_wgrad_split_kernel<2, 2>
+  kWgradFamSplit21 = 3,
+  kWgradFamSplit12 = 4,
+  kWgradFamSplit11 = 5,
+  kWgradFamSplitOcc3 = 6,  // conv_wgrad_split_kernel<2, 2, 3>
+  kWgradFamilies = 7,
+  kWgradFamNone = -1,  // the f32 kernels: launched alone
+};
+inline int wgrad_family(const WgradPlan& p) {
+  switch (p.kernel) {
+    case kWgradWS: return kWgradFamWS;
+    case kWgradWSInc: return kWgradFamWSInc;
+    case kWgradSplitOcc3: return kWgradFamSplitOcc3;
+    case kWgradSplit:
+      return p.TM == 2 ? (p.TN == 2 ? kWgradFamSplit22 : kWgradFamSplit21)
+                       : (p.TN == 2 ? kWgradFamSplit12 : kWgradFamSplit11);
+    default: return kWgradFamNone;
+  }
+}
+// Resident workgroups of a family's kernel on 256 CUs (plan_wgrad's G).
+inline int wgrad_family_slots(int family) {
+  return family <= kWgradFamWSInc ? 256 : (family == kWgradFamSplitOcc3 ? 768 : 512);
+}
+struct WgradGroupFamily {
+  int count;              // problems of the family (0: no launch)
+  int nwg;                // workgroups of the grouped launch
+  int chunks_per_split;   // common to the family's problems
+  int reduce_problems;    // problems that go through slabs
+  long long reduce_items; // float4s of dw + bias elements over those problems
+  int reduce_grid;
+  size_t slab_off, slab_floats;  // the family's block of the workspace, in floats
+};
+struct WgradGroupPlan {
+  int n, grouped;  // grouped 0: every problem runs its own plan_wgrad plan, alone
+  WgradPlan p[kMaxWgradGroup];        // own geometry; splits / chunks_per_split / part of the group
+  int family[kMaxWgradGroup];         // WgradFamily
+  int wg0[kMaxWgradGroup];            // first workgroup in the family's launch
+  size_t slab_off[kMaxWgradGroup];    // floats from the workspace start: [splits][wsize] dw
+                                      // partials, then [splits][Cout] bias partials
+  long long item0[kMaxWgradGroup];    // first item of the family's reduce (-1: no slabs)
+  WgradGroupFamily fam[kWgradFamilies];
+  size_t ws_bytes;
+};
+
+// The total order the plan walks the problems in, so that it does not depend
+// on the order they are given in: by shape (equal shapes get equal plans, and
+// their relative order only permutes equal entries).
+inline bool wgrad_shape_less(const ConvShape& a, const ConvShape& b) {
+  const int ka[] = {a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride, a.pad_beg, a.pad_end};
+  const int kb[] = {b.N, b.H, b.W, b.Cin, b.Cout, b.KH, b.KW, b.stride, b.pad_beg, b.pad_end};
+  return std::lexicographical_compare(ka, ka + 10, kb, kb + 10);
+}
+
+// Workgroups of a family at `per` chunks per split.
+inline long long wgrad_group_wgs(const WgradGroupPlan& g, int family, int per) {
+  long long w = 0;
+  for (int i = 0; i < g.n; ++i)
+    if (g.family[i] == family) w += (long long)g.p[i].ntiles * ((g.p[i].nchunks + per - 1) / per);
+  return w;
+}
+
+// flags: d2mi_conv2d_wgrad_ex's without the accumulate bit; operands:
+// kOpWorkspace, kOpWsAligned (a workspace that is not 16-B aligned counts as
+// none).  A group of one, and a missing or short workspace, give each problem
+// its own plan_wgrad plan (grouped = 0).  -1: a bad shape or too many problems.
+inline int plan_wgrad_group(const ConvShape* shapes, int n, int flags, int operands,
+                            size_t workspace_bytes, int cus, WgradGroupPlan* out) {
+  WgradGroupPlan& g = *out;
+  g = {};
+  if (n <= 0 || n > kMaxWgradGroup) return -1;
+  g.n = n;
+  const size_t own_ws = (operands & kOpWorkspace) ? workspace_bytes : 0;
+  for (int i = 0; i < n; ++i) {
+    if (plan_wgrad(shapes[i], flags, operands | kOpAligned, own_ws, &g.p[i])) return -1;
+    g.family[i] = wgrad_family(g.p[i]);
+    g.item0[i] = -1;
+  }
+  const bool usable = (operands & kOpWorkspace) && (operands & kOpWsAligned);
+  if (n == 1 || !usable || (flags & kPlanAccum)) return 0;
+  // tuning "wgrad_group" 1: the problems keep the splits of their own plans and
+  // only share the launches (and one reduce per family) -- every gradient has
+  // the bits of its single launch; 2: one chunks-per-split per family, chosen
+  // below -- long walks and few slabs, but other pixel ranges per partial sum,
+  // so the gradients differ from the single launches' in the last bits
+  const bool common = tuning(kTuneWgradGroup) >= 2;
+  WgradGroupPlan t = g;
+  const int minch = tuning(kTuneWgradMinCh) > 0 ? tuning(kTuneWgradMinCh) : 16;
+  const int maxsplit = tuning(kTuneWgradMaxSplit) > 0 ? tuning(kTuneWgradMaxSplit) : 128;
+  for (int f = 0; f < kWgradFamilies; ++f) {
+    int count = 0, lo = minch, longest = 1, only = -1;
+    for (int i = 0; i < n; ++i) {
+      if (t.family[i] != f) continue;
+      ++count;
+      only = i;
+      longest = std::max(longest, t.p[i].nchunks);
+      lo = std::max(lo, (t.p[i].nchunks + maxsplit - 1) / maxsplit);
+    }
+    t.fam[f].count = count;
+    if (count == 0) continue;
+    int per;
+    if (!common) {
+      per = 0;  // every problem its own plan's splits: the single launches' sums, bit for bit
+    } else if (count == 1) {
+      per = t.p[only].chunks_per_split;  // alone in its family: its own plan
+    } else {
+      // resident workgroups: the kernel's per-CU count on this device (tuning
+      // "wgrad_slots" overrides it, as in plan_wgrad)
+      const int G = tuning(kTuneWgradSlots) > 0 ? tuning(kTuneWgradSlots)
+                                                : wgrad_family_slots(f) / 256 * std::max(cus, 1);
+      // The launch's time in chunk steps: rounds of resident workgroups x
+      // (chunks per split + kWgradGroupFixed, a workgroup's prologue and
+      // epilogue in chunk steps).  The candidates are the lengths that cut
+      // some problem into whole splits, from two rounds' length down to the
+      // shortest allowed and up to one split per problem; the cheapest wins,
+      // the longer of equals (fewer slabs): totals that just fill whole
+      // rounds, walks long enough to amortise the fixed part.
+      lo = std::min(lo, longest);
+      long long best = -1;
+      per = longest;
+      for (int i = 0; i < n; ++i) {
+        bool seen = t.family[i] != f;  // (a pixel count already tried)
+        for (int j = 0; j < i && !seen; ++j)
+          seen = t.family[j] == f && t.p[j].nchunks == t.p[i].nchunks;
+        if (seen) continue;
+        // (as plan_wgrad: at most nchunks / minch splits of the problem itself)
+        const int kmax = std::min(maxsplit, std::max(1, t.p[i].nchunks / minch));
+        for (int k = 1; k <= kmax; ++k) {
+          const int c = (t.p[i].nchunks + k - 1) / k;
+          if (c < lo) break;
+          const long long w = wgrad_group_wgs(t, f, c);
+          const long long cost = (w + G - 1) / G * (c + kWgradGroupFixed);
+          if (best < 0 || cost < best || (cost == best && c > per)) best = cost, per = c;
+        }
+      }
+    }
+    t.fam[f].chunks_per_split = per;
+  }
+  // per problem: splits, first workgroup, slab and reduce offsets, in shape order
+  int order[kMaxWgradGroup];
+  for (int i = 0; i < n; ++i) order[i] = i;
+  std::stable_sort(order, order + n,
+                   [&](int a, int b) { return wgrad_shape_less(shapes[a], shapes[b]); });
+  size_t off = 0;  // floats
+  for (int f = 0; f < kWgradFamilies; ++f) {
+    WgradGroupFamily& F = t.fam[f];
+    if (F.count == 0) continue;
+    F.slab_off = off;
+    for (int k = 0; k < n; ++k) {
+      const int i = order[k];
+      if (t.family[i] != f) continue;
+      WgradPlan& p = t.p[i];
+      if (F.chunks_per_split > 0) {
+        p.splits = (p.nchunks + F.chunks_per_split - 1) / F.chunks_per_split;
+        p.chunks_per_split = F.chunks_per_split;
+      }
+      p.part = p.splits > 1;
+      p.reduce = p.part ? kReduceFloat4 : kReduceNone;
+      p.reduce_grid = 0;
+      const ConvShape& s = shapes[i];
+      const size_t wsize = (size_t)s.KH * s.KW * s.Cin * s.Cout;
+      p.ws_bytes = p.part ? (size_t)p.splits * (wsize + s.Cout) * 4 : 0;
+      t.wg0[i] = F.nwg;
+      F.nwg += p.ntiles * p.splits;
+      if (p.part) {
+        t.slab_off[i] = off;
+        off += (size_t)p.splits * (wsize + s.Cout);
+        t.item0[i] = F.reduce_items;
+        F.reduce_items += (long long)(wsize / 4) + s.Cout;
+        ++F.reduce_problems;
+      }
+    }
+    F.slab_floats = off - F.slab_off;
+    F.reduce_grid = (int)std::min<long long>((F.reduce_items + 255) / 256, 8192);
+  }
+  t.ws_bytes = off * 4;
+  if (t.ws_bytes > workspace_bytes) return 0;  // short workspace: the ungrouped plans
+  t.grouped = 1;
+  g = t;
+  return 0;
+}
+
 }  // namespace d2mi

@@ -299,17 +299,18 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {
   return (__umulhi(n, f.m) + n) >> f.l;
 }
 
-template <int TM, int TN, int OCC = 2>
-__global__ __launch_bounds__(256, OCC) void conv_wgrad_split_kernel(WgradArgs a, FastDiv fd_hw,
-                                                                    FastDiv fd_w) {
+// The work of one workgroup: output tile `tile` of problem `a` over pixel
+// split `split` (the body of conv_wgrad_split_kernel and of its grouped form).
+template <int TM, int TN>
+__device__ __forceinline__ void wgrad_split_body(const WgradArgs& a, const FastDiv& fd_hw,
+                                                 const FastDiv& fd_w, const int tile,
+                                                 const int split) {
   constexpr int BM = 2 * TM * 32, BN = 2 * TN * 32;
   constexpr int GA = BM / 4, GB = BN / 4;  // 4-channel groups
   __shared__ __attribute__((aligned(16))) uint16_t As[3 * BM * LDW];
   __shared__ __attribute__((aligned(16))) uint16_t Bs[3 * BN * LDW];
   __shared__ float bred[8][BN];
 
-  int tile, split;
-  wgrad_tile_split(a, tile, split);
   const int per_tap = a.nCi * a.nCo;
   const int tap = tile / per_tap;
   const int rem = tile - tap * per_tap;
@@ -464,6 +465,14 @@ __global__ __launch_bounds__(256, OCC) void conv_wgrad_split_kernel(WgradArgs a,
   }
 }
 
+template <int TM, int TN, int OCC = 2>
+__global__ __launch_bounds__(256, OCC) void conv_wgrad_split_kernel(WgradArgs a, FastDiv fd_hw,
+                                                                    FastDiv fd_w) {
+  int tile, split;
+  wgrad_tile_split(a, tile, split);
+  wgrad_split_body<TM, TN>(a, fd_hw, fd_w, tile, split);
+}
+
 
 // Warp-specialised split wgrad (the conv_ws_kernel structure of
 // conv_mfma.hip for the weight gradient): a 256 (ci) x 128 (co) tile of one
@@ -486,9 +495,10 @@ __global__ __launch_bounds__(256, OCC) void conv_wgrad_split_kernel(WgradArgs a,
 // that start at +0 and can never become -0, so for finite x the sums (and the
 // bias sums) are bit-identical to the dense walk.  A split without a set
 // chunk still writes its zero slab.
-template <int LD, bool INC = false, bool LIST = false>
-__global__ __launch_bounds__(1024, 1) void conv_wgrad_ws_kernel(WgradArgs a, FastDiv fd_hw,
-                                                                FastDiv fd_w) {
+template <int LD, bool INC, bool LIST>
+__device__ __forceinline__ void wgrad_ws_body(const WgradArgs& a, const FastDiv& fd_hw,
+                                              const FastDiv& fd_w, const int tile,
+                                              const int split) {
   static_assert(!(LIST && INC), "the listed chunks are not consecutive");
   constexpr int TM = 2, TN = 2, BM = 256, BN = 128, S = 2;
   constexpr int GA = BM / 4, GB = BN / 4;  // 4-channel groups
@@ -500,8 +510,6 @@ __global__ __launch_bounds__(1024, 1) void conv_wgrad_ws_kernel(WgradArgs a, Fas
   __shared__ uint16_t clist[LIST ? kWgradListCap : 1];
   __shared__ int wcnt[LIST ? 17 : 1];
 
-  int tile, split;
-  wgrad_tile_split(a, tile, split);
   const int per_tap = a.nCi * a.nCo;
   const int tap = tile / per_tap;
   const int rem = tile - tap * per_tap;
@@ -782,6 +790,132 @@ __global__ __launch_bounds__(1024, 1) void conv_wgrad_ws_kernel(WgradArgs a, Fas
   }
 }
 
+template <int LD, bool INC = false, bool LIST = false>
+__global__ __launch_bounds__(1024, 1) void conv_wgrad_ws_kernel(WgradArgs a, FastDiv fd_hw,
+                                                                FastDiv fd_w) {
+  int tile, split;
+  wgrad_tile_split(a, tile, split);
+  wgrad_ws_body<LD, INC, LIST>(a, fd_hw, fd_w, tile, split);
+}
+
+// ---------------------------------------------------------------------------
+// Grouped forms (d2mi_conv2d_wgrad_group): the problems of one kernel family
+// in one grid.  The launch reads a device table: the first workgroup of each
+// problem (ascending), then one WgradGroupEntry per problem.  Logical order:
+// the problems concatenated, split-major, tile fastest, and the linear
+// workgroup id remapped XCD-contiguously over the whole grid as
+// wgrad_tile_split does for one problem -- the tiles of one problem's pixel
+// range stay on one XCD.  The problem is found by a wave-uniform binary search
+// of the prefix and its arguments are read through uniform loads; the work is
+// the single launch's body, so equal splits give equal bits.
+struct WgradGroupEntry {
+  WgradArgs a;
+  FastDiv fd_hw, fd_w;
+};
+struct WgradGroupTable {
+  int wg0[kMaxWgradGroup];  // [n] first workgroup of each problem
+  WgradGroupEntry e[1];     // [n]
+};
+
+__device__ __forceinline__ int wgrad_group_locate(const WgradGroupTable* __restrict__ t, int n,
+                                                  int nwg, int xcd, int& local) {
+  const int L = blockIdx.x;
+  int l = L;
+  if (xcd) {
+    const int q = nwg / 8, r8 = nwg % 8, x8 = L % 8;
+    l = (x8 < r8 ? x8 * (q + 1) : r8 * (q + 1) + (x8 - r8) * q) + L / 8;
+  }
+  int lo = 0, hi = n;  // the last problem whose first workgroup is <= l
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (t->wg0[mid] <= l) lo = mid;
+    else hi = mid;
+  }
+  lo = __builtin_amdgcn_readfirstlane(lo);
+  local = l - t->wg0[lo];
+  return lo;
+}
+
+template <int TM, int TN, int OCC = 2>
+__global__ __launch_bounds__(256, OCC) void conv_wgrad_split_group_kernel(
+    const WgradGroupTable* __restrict__ t, int n, int nwg, int xcd) {
+  int local;
+  const int i = wgrad_group_locate(t, n, nwg, xcd, local);
+  const WgradGroupEntry& e = t->e[i];
+  const int split = local / e.a.ntiles;
+  wgrad_split_body<TM, TN>(e.a, e.fd_hw, e.fd_w, local - split * e.a.ntiles, split);
+}
+
+template <int LD, bool INC>
+__global__ __launch_bounds__(1024, 1) void conv_wgrad_ws_group_kernel(
+    const WgradGroupTable* __restrict__ t, int n, int nwg, int xcd) {
+  int local;
+  const int i = wgrad_group_locate(t, n, nwg, xcd, local);
+  const WgradGroupEntry& e = t->e[i];
+  const int split = local / e.a.ntiles;
+  wgrad_ws_body<LD, INC, false>(e.a, e.fd_hw, e.fd_w, local - split * e.a.ntiles, split);
+}
+
+// The reduce of one family's slabs: a flat index over the float4s of every
+// problem's dw, each followed by its Cout bias elements (items [item0[i],
+// item0[i + 1]) are problem i's).  Splits are summed in ascending order from
+// 0.f, as wgrad_reduce4_kernel and wgrad_reduce_kernel do; a dw that is not
+// 16-B aligned (a view into a gradient bucket) gets the same sums by four
+// scalar stores.
+struct WgradReduceEntry {
+  const float* partial;  // [splits][4 * total4]
+  const float* pbias;    // [splits][Cout]
+  float* dw;
+  float* dbias;  // nullable
+  int splits, total4, Cout, pad_;
+};
+struct WgradReduceTable {
+  int item0[kMaxWgradGroup + 1];  // [n + 1]
+  int pad_;
+  WgradReduceEntry e[1];  // [n]
+};
+__global__ void wgrad_group_reduce4_kernel(const WgradReduceTable* __restrict__ t, int n) {
+  const int total = t->item0[n];
+  for (int it = blockIdx.x * blockDim.x + threadIdx.x; it < total; it += gridDim.x * blockDim.x) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (t->item0[mid] <= it) lo = mid;
+      else hi = mid;
+    }
+    const WgradReduceEntry& e = t->e[lo];
+    const int j = it - t->item0[lo];
+    const int splits = e.splits, total4 = e.total4;
+    if (j < total4) {
+      const float4* __restrict__ partial = reinterpret_cast<const float4*>(e.partial);
+      float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4
+      for (int k = 0; k < splits; ++k) {
+        const float4 v = partial[(size_t)k * total4 + j];
+        s.x += v.x;
+        s.y += v.y;
+        s.z += v.z;
+        s.w += v.w;
+      }
+      float* dw = e.dw + 4 * (size_t)j;
+      if (((uintptr_t)e.dw & 15) == 0) {
+        *reinterpret_cast<float4*>(dw) = s;
+      } else {
+        dw[0] = s.x;
+        dw[1] = s.y;
+        dw[2] = s.z;
+        dw[3] = s.w;
+      }
+    } else if (e.dbias != nullptr) {
+      const int c = j - total4;
+      float s = 0.f;
+#pragma unroll 8  // (loads in flight; the sum stays in split order)
+      for (int k = 0; k < splits; ++k) s += e.pbias[(size_t)k * e.Cout + c];
+      e.dbias[c] = s;
+    }
+  }
+}
+
 FastDiv make_fastdiv(uint32_t d) {
   FastDiv f;
   f.d = d;
@@ -852,6 +986,46 @@ extern "C" int d2mi_conv2d_wgrad_plan(int N, int H, int W, int Cin, int Cout, in
   return emit_plan(v, (int)(sizeof(v) / sizeof(v[0])), out, out_len);
 }
 
+// The kernel arguments of one problem under plan p (partial / pbias: its slabs
+// when p.part).
+static WgradArgs wgrad_args(const float* x, const float* dy, float* dw, float* dbias,
+                            const ConvShape& s, const WgradPlan& p, float* partial,
+                            float* pbias) {
+  WgradArgs a = {};
+  a.prio = tuning(kTuneWgradPrio);
+  a.xcd = tuning(kTuneWgradXCD) > 0 ? 1 : 0;
+  a.x = x;
+  a.dy = dy;
+  a.dw = dw;
+  a.dbias = dbias;
+  a.N = s.N;
+  a.H = s.H;
+  a.W = s.W;
+  a.Cin = s.Cin;
+  a.Cout = s.Cout;
+  a.KH = s.KH;
+  a.KW = s.KW;
+  a.stride = s.stride;
+  a.pad = s.pad_beg;
+  a.OH = p.OH;
+  a.OW = p.OW;
+  a.P = s.N * a.OH * a.OW;
+  a.nCi = p.nCi;
+  a.nCo = p.nCo;
+  a.ntiles = p.ntiles;
+  a.splits = p.splits;
+  a.chunks_per_split = p.chunks_per_split;
+  a.nchunks = p.nchunks;
+  a.part = p.part;
+  a.partial = partial;
+  a.pbias = pbias;
+  if (p.kernel != kWgradF32) {
+    a.x_bytes = (int)((int64_t)s.N * s.H * s.W * s.Cin * 4);
+    a.dy_bytes = (int)((int64_t)a.P * s.Cout * 4);
+  }
+  return a;
+}
+
 // d2mi_conv2d_wgrad_ex, and with a chunk bitmap d2mi_conv2d_wgrad_rows: the
 // same plan either way.  Returns 1 when the bitmap kernel ran, 0 after the
 // dense launch (kernels other than the warp-specialised one ignore the
@@ -873,40 +1047,11 @@ static int wgrad_launch(const float* x, const float* dy, float* dw_hwio, float* 
     Workspace carve(workspace, workspace_bytes);
     sp.lay(carve, p.splits, (size_t)KH * KW * Cin * Cout, Cout);
   }
-  WgradArgs a = {};
-  a.prio = tuning(kTuneWgradPrio);
-  a.xcd = tuning(kTuneWgradXCD) > 0 ? 1 : 0;
-  a.x = x;
-  a.dy = dy;
-  a.dw = dw_hwio;
-  a.dbias = dbias;
-  a.N = N;
-  a.H = H;
-  a.W = W;
-  a.Cin = Cin;
-  a.Cout = Cout;
-  a.KH = KH;
-  a.KW = KW;
-  a.stride = stride;
-  a.pad = pad_beg;
-  a.OH = p.OH;
-  a.OW = p.OW;
-  a.P = N * a.OH * a.OW;
-  a.nCi = p.nCi;
-  a.nCo = p.nCo;
-  a.ntiles = p.ntiles;
-  a.splits = p.splits;
-  a.chunks_per_split = p.chunks_per_split;
-  a.nchunks = p.nchunks;
-  a.part = p.part;
-  a.partial = sp.dw;
-  a.pbias = sp.dbias;
+  WgradArgs a = wgrad_args(x, dy, dw_hwio, dbias,
+                           {N, H, W, Cin, Cout, KH, KW, stride, pad_beg, pad_end}, p, sp.dw,
+                           sp.dbias);
   hipStream_t st = as_stream(stream);
   const dim3 grid(p.ntiles, p.splits);
-  if (p.kernel != kWgradF32) {
-    a.x_bytes = (int)((int64_t)N * H * W * Cin * 4);
-    a.dy_bytes = (int)((int64_t)a.P * Cout * 4);
-  }
   const FastDiv fhw = make_fastdiv((uint32_t)(a.OH * a.OW)), fw = make_fastdiv((uint32_t)a.OW);
   const int tm = p.TM, tn = p.TN;
   const bool listed = bitmap != nullptr && p.chunks_per_split <= kWgradListCap &&
@@ -987,4 +1132,245 @@ extern "C" int d2mi_conv2d_wgrad(const float* x, const float* dy, float* dw_hwio
                                  size_t workspace_bytes, void* stream) {
   return d2mi_conv2d_wgrad_ex(x, dy, dw_hwio, dbias, N, H, W, Cin, Cout, KH, KW, stride,
                               pad_beg, pad_end, 0, workspace, workspace_bytes, stream);
+}
+
+// ---- grouped weight gradients
+namespace {
+
+struct WgradProblem {  // the host array of d2mi_conv2d_wgrad_group (include/d2mi.h)
+  const float* x;
+  const float* dy;
+  float* dw;
+  float* dbias;
+  int32_t N, H, W, Cin, Cout, KH, KW, stride, pad_beg, pad_end;
+};
+static_assert(sizeof(WgradProblem) == 72, "d2mi_conv2d_wgrad_group: problem layout");
+
+// The most workspace d2mi_conv2d_wgrad_group_workspace_size asks for.
+constexpr size_t kWgradGroupMaxWorkspace = (size_t)1 << 30;
+
+// The device table: per family the launch's table, then its reduce's.
+struct WgradGroupLayout {
+  size_t launch[kWgradFamilies], reduce[kWgradFamilies], bytes;
+  explicit WgradGroupLayout(const int* count) {
+    size_t off = 0;
+    for (int f = 0; f < kWgradFamilies; ++f) {
+      launch[f] = off;
+      if (count[f]) off = align_up(off + offsetof(WgradGroupTable, e) + count[f] * sizeof(WgradGroupEntry), 16);
+      reduce[f] = off;
+      if (count[f]) off = align_up(off + offsetof(WgradReduceTable, e) + count[f] * sizeof(WgradReduceEntry), 16);
+    }
+    bytes = off;
+  }
+};
+size_t wgrad_group_table_bytes(int n) {
+  // every family non-empty, n entries in all, and the 16-B rounding of each block
+  return kWgradFamilies * (offsetof(WgradGroupTable, e) + offsetof(WgradReduceTable, e) + 32) +
+         (size_t)n * (sizeof(WgradGroupEntry) + sizeof(WgradReduceEntry));
+}
+
+ConvShape shape_of(const WgradProblem& q) {
+  return {q.N, q.H, q.W, q.Cin, q.Cout, q.KH, q.KW, q.stride, q.pad_beg, q.pad_end};
+}
+
+int wgrad_group_cus() {
+  int dev = 0, c = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0) {
+    (void)hipGetLastError();
+    return 256;  // (plan queries without a GPU)
+  }
+  return c;
+}
+
+// The checks of every problem that need no pointer, then the group's plan.
+int wgrad_group_plan_checked(const WgradProblem* q, int n, int flags, int operands,
+                             size_t workspace_bytes, WgradGroupPlan* g) {
+  D2MI_REQUIRE(q != nullptr && n > 0 && n <= kMaxWgradGroup,
+               "wgrad group: 1..%d problems (got %d)", kMaxWgradGroup, n);
+  D2MI_REQUIRE((flags & ~4) == 0, "wgrad group flags: bit2 = split-bf16 products");
+  ConvShape shapes[kMaxWgradGroup];
+  WgradPlan p;
+  for (int i = 0; i < n; ++i) {
+    if (wgrad_plan_checked(q[i].N, q[i].H, q[i].W, q[i].Cin, q[i].Cout, q[i].KH, q[i].KW,
+                           q[i].stride, q[i].pad_beg, q[i].pad_end, flags, 0, 0, &p))
+      return -1;
+    shapes[i] = shape_of(q[i]);
+  }
+  static const int cus = wgrad_group_cus();
+  D2MI_REQUIRE(plan_wgrad_group(shapes, n, flags, operands, workspace_bytes, cus, g) == 0,
+               "wgrad group: no plan");
+  return 0;
+}
+
+int wgrad_group_operands(const void* workspace) {
+  return (workspace ? kOpWorkspace : 0) | (((uintptr_t)workspace & 15) == 0 ? kOpWsAligned : 0);
+}
+
+template <typename K>
+void launch_group(K kernel, int threads, const WgradGroupFamily& F, const void* table, int xcd,
+                  hipStream_t st) {
+  hipLaunchKernelGGL(kernel, dim3(F.nwg), dim3(threads), 0, st,
+                     reinterpret_cast<const WgradGroupTable*>(table), F.count, F.nwg, xcd);
+}
+
+}  // namespace
+
+extern "C" size_t d2mi_conv2d_wgrad_group_table_size(int n) {
+  return n > 0 && n <= kMaxWgradGroup ? wgrad_group_table_bytes(n) : 0;
+}
+
+extern "C" size_t d2mi_conv2d_wgrad_group_workspace_size(const void* problems, int n, int flags) {
+  const WgradProblem* q = reinterpret_cast<const WgradProblem*>(problems);
+  WgradGroupPlan g;
+  // (asked for at most kWgradGroupMaxWorkspace: a group whose slabs need more
+  // -- every problem's at once, under the default -- runs as single launches)
+  if (wgrad_group_plan_checked(q, n, flags, kOpWorkspace | kOpWsAligned, kWgradGroupMaxWorkspace,
+                               &g))
+    return 0;
+  // the group's slabs, or the largest of the problems that run alone
+  size_t bytes = g.grouped ? g.ws_bytes : 0;
+  for (int i = 0; i < n; ++i)
+    if (!g.grouped || g.family[i] == kWgradFamNone)
+      bytes = std::max(bytes, d2mi_conv2d_wgrad_workspace_size(q[i].N, q[i].H, q[i].W, q[i].Cin,
+                                                               q[i].Cout, q[i].KH, q[i].KW,
+                                                               q[i].stride, q[i].pad_beg,
+                                                               q[i].pad_end));
+  return bytes;
+}
+
+extern "C" int d2mi_conv2d_wgrad_group_plan(const void* problems, int n, int flags, int operands,
+                                            size_t workspace_bytes, int32_t* out, int out_len) {
+  D2MI_REQUIRE((operands & ~127) == 0, "wgrad group plan: unknown operand bits");
+  WgradGroupPlan g;
+  if (wgrad_group_plan_checked(reinterpret_cast<const WgradProblem*>(problems), n, flags,
+                               operands, workspace_bytes, &g))
+    return -1;
+  int32_t v[2 + 6 * kWgradFamilies + 9 * kMaxWgradGroup + 2];
+  int k = 0;
+  v[k++] = g.grouped;
+  v[k++] = n;
+  for (int f = 0; f < kWgradFamilies; ++f) {
+    const WgradGroupFamily& F = g.fam[f];
+    const int32_t fv[] = {F.count, F.nwg, F.chunks_per_split, F.reduce_problems, F.reduce_grid, 0};
+    for (int32_t x : fv) v[k++] = g.grouped ? x : 0;
+  }
+  size_t ws = g.grouped ? g.ws_bytes : 0;
+  for (int i = 0; i < n; ++i) {
+    const WgradPlan& p = g.p[i];
+    const size_t off = g.grouped && p.part ? g.slab_off[i] * 4 : 0;
+    const int32_t pv[] = {g.grouped ? g.family[i] : kWgradFamNone, p.kernel, p.ntiles, p.nchunks,
+                          p.splits, p.chunks_per_split, g.grouped ? g.wg0[i] : 0,
+                          (int32_t)(off & 0x7fffffff), (int32_t)(off >> 31)};
+    for (int32_t x : pv) v[k++] = x;
+    if (!g.grouped) ws = std::max(ws, p.ws_bytes);
+  }
+  v[k++] = (int32_t)(ws & 0x7fffffff);
+  v[k++] = (int32_t)(ws >> 31);
+  return emit_plan(v, k, out, out_len);
+}
+
+extern "C" int d2mi_conv2d_wgrad_group_table(const void* problems, int n, int flags,
+                                             void* workspace, size_t workspace_bytes,
+                                             void* table_host, size_t table_bytes) {
+  const WgradProblem* q = reinterpret_cast<const WgradProblem*>(problems);
+  WgradGroupPlan g;
+  if (wgrad_group_plan_checked(q, n, flags, wgrad_group_operands(workspace), workspace_bytes, &g))
+    return -1;
+  D2MI_REQUIRE(table_host != nullptr && table_bytes >= wgrad_group_table_bytes(n),
+               "wgrad group table too small (%zu < %zu)", table_bytes, wgrad_group_table_bytes(n));
+  std::fill_n(reinterpret_cast<char*>(table_host), table_bytes, (char)0);
+  if (!g.grouped) return 0;  // every problem runs alone: no table is read
+  int count[kWgradFamilies];
+  for (int f = 0; f < kWgradFamilies; ++f) count[f] = g.fam[f].count;
+  const WgradGroupLayout lay(count);
+  char* base = reinterpret_cast<char*>(table_host);
+  float* ws = reinterpret_cast<float*>(workspace);
+  for (int f = 0; f < kWgradFamilies; ++f) {
+    if (!count[f]) continue;
+    WgradGroupTable* lt = reinterpret_cast<WgradGroupTable*>(base + lay.launch[f]);
+    WgradReduceTable* rt = reinterpret_cast<WgradReduceTable*>(base + lay.reduce[f]);
+    // the family's problems by first workgroup (the plan's shape order)
+    int idx[kMaxWgradGroup], m = 0;
+    for (int i = 0; i < n; ++i)
+      if (g.family[i] == f) idx[m++] = i;
+    std::sort(idx, idx + m, [&](int a, int b) { return g.wg0[a] < g.wg0[b]; });
+    int r = 0;
+    for (int k = 0; k < m; ++k) {
+      const int i = idx[k];
+      const WgradPlan& p = g.p[i];
+      const size_t wsize = (size_t)q[i].KH * q[i].KW * q[i].Cin * q[i].Cout;
+      float* partial = p.part ? ws + g.slab_off[i] : nullptr;
+      float* pbias = p.part ? partial + (size_t)p.splits * wsize : nullptr;
+      lt->wg0[k] = g.wg0[i];
+      lt->e[k].a = wgrad_args(q[i].x, q[i].dy, q[i].dw, q[i].dbias, shape_of(q[i]), p, partial,
+                              pbias);
+      lt->e[k].fd_hw = make_fastdiv((uint32_t)(p.OH * p.OW));
+      lt->e[k].fd_w = make_fastdiv((uint32_t)p.OW);
+      if (!p.part) continue;
+      rt->item0[r] = (int)g.item0[i];
+      rt->e[r] = {partial, pbias, q[i].dw, q[i].dbias, p.splits, (int)(wsize / 4), q[i].Cout, 0};
+      ++r;
+    }
+    rt->item0[r] = (int)g.fam[f].reduce_items;
+  }
+  return 0;
+}
+
+extern "C" int d2mi_conv2d_wgrad_group(const void* problems, int n, int flags,
+                                       const void* table_dev, size_t table_bytes, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  const WgradProblem* q = reinterpret_cast<const WgradProblem*>(problems);
+  WgradGroupPlan g;
+  if (wgrad_group_plan_checked(q, n, flags, wgrad_group_operands(workspace), workspace_bytes, &g))
+    return -1;
+  for (int i = 0; i < n; ++i)
+    D2MI_REQUIRE(q[i].x && q[i].dy && q[i].dw && ((uintptr_t)q[i].x & 15) == 0 &&
+                     ((uintptr_t)q[i].dy & 15) == 0 && ((uintptr_t)q[i].dw & 3) == 0,
+                 "wgrad group: problem %d: x and dy must be 16-byte aligned, dw given", i);
+  auto alone = [&](int i) {
+    return wgrad_launch(q[i].x, q[i].dy, q[i].dw, q[i].dbias, q[i].N, q[i].H, q[i].W, q[i].Cin,
+                        q[i].Cout, q[i].KH, q[i].KW, q[i].stride, q[i].pad_beg, q[i].pad_end,
+                        flags, nullptr, workspace, workspace_bytes, stream);
+  };
+  if (!g.grouped) {
+    for (int i = 0; i < n; ++i)
+      if (alone(i) < 0) return -1;
+    return 0;
+  }
+  D2MI_REQUIRE(table_dev != nullptr && table_bytes >= wgrad_group_table_bytes(n) &&
+                   ((uintptr_t)table_dev & 15) == 0,
+               "wgrad group: the device table must hold %zu bytes, 16-byte aligned",
+               wgrad_group_table_bytes(n));
+  D2MI_REQUIRE(g.ws_bytes <= workspace_bytes, "wgrad group workspace too small (%zu < %zu)",
+               workspace_bytes, g.ws_bytes);
+  int count[kWgradFamilies];
+  for (int f = 0; f < kWgradFamilies; ++f) count[f] = g.fam[f].count;
+  const WgradGroupLayout lay(count);
+  const char* base = reinterpret_cast<const char*>(table_dev);
+  hipStream_t st = as_stream(stream);
+  const int xcd = tuning(kTuneWgradXCD) > 0 ? 1 : 0;
+  for (int f = 0; f < kWgradFamilies; ++f) {
+    const WgradGroupFamily& F = g.fam[f];
+    if (!F.count) continue;
+    const void* lt = base + lay.launch[f];
+    switch (f) {
+      case kWgradFamWS: launch_group(conv_wgrad_ws_group_kernel<1, false>, 1024, F, lt, xcd, st); break;
+      case kWgradFamWSInc: launch_group(conv_wgrad_ws_group_kernel<1, true>, 1024, F, lt, xcd, st); break;
+      case kWgradFamSplit22: launch_group(conv_wgrad_split_group_kernel<2, 2>, 256, F, lt, xcd, st); break;
+      case kWgradFamSplit21: launch_group(conv_wgrad_split_group_kernel<2, 1>, 256, F, lt, xcd, st); break;
+      case kWgradFamSplit12: launch_group(conv_wgrad_split_group_kernel<1, 2>, 256, F, lt, xcd, st); break;
+      case kWgradFamSplit11: launch_group(conv_wgrad_split_group_kernel<1, 1>, 256, F, lt, xcd, st); break;
+      default: launch_group(conv_wgrad_split_group_kernel<2, 2, 3>, 256, F, lt, xcd, st); break;
+    }
+    D2MI_LAUNCH_CHECK();
+    if (F.reduce_problems == 0) continue;
+    hipLaunchKernelGGL(wgrad_group_reduce4_kernel, dim3(F.reduce_grid), dim3(256), 0, st,
+                       reinterpret_cast<const WgradReduceTable*>(base + lay.reduce[f]),
+                       F.reduce_problems);
+    D2MI_LAUNCH_CHECK();
+  }
+  for (int i = 0; i < n; ++i)  // the f32 kernels: alone, after the slabs were reduced
+    if (g.family[i] == kWgradFamNone && alone(i) < 0) return -1;
+  return 0;
 }

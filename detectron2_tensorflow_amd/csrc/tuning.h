@@ -27,7 +27,12 @@ namespace d2mi {
 // workgroup target (0: the plan's own); conv_tail: 0 no tail split;
 // wgrad_occ3_min_p: the pixel count from which the 3-per-CU wgrad runs;
 // wgrad_minch / wgrad_maxsplit: fewest chunks per split / most splits (<= 0:
-// the default); wgrad_prio: MFMA wave priority; topk_floor: 0 = radix passes only
+// the default); wgrad_prio: MFMA wave priority; topk_floor: 0 = radix passes only;
+// wgrad_group: the folded backbone convs' weight gradients deferred to the
+// fold's backward and launched per kernel family (d2mi_conv2d_wgrad_group):
+// 1 = each with the pixel splits of its own plan (the bits of the single
+// launches), 2 = one chunks-per-split per family (fewer slabs, longer walks,
+// other rounding); 0 = each in its own conv's backward
 #define D2MI_TUNE_KNOBS(X)                       \
   X(kTuneConvEpi, "conv_epi", 1)                 \
   X(kTuneWgradWS1, "wgrad_ws1", 6)               \
@@ -55,7 +60,8 @@ namespace d2mi {
   X(kTuneWgradMinCh, "wgrad_minch", 16)          \
   X(kTuneWgradMaxSplit, "wgrad_maxsplit", 128)   \
   X(kTuneWgradPrio, "wgrad_prio", 1)             \
-  X(kTuneTopkFloor, "topk_floor", 1)
+  X(kTuneTopkFloor, "topk_floor", 1)             \
+  X(kTuneWgradGroup, "wgrad_group", 1)
 enum TuneKey {
 #define X(id, key, def) id,
   D2MI_TUNE_KNOBS(X)

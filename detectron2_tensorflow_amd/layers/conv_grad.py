@@ -75,35 +75,45 @@ def _wgrad(x, gy, w_shape, stride, pb, pe, want_bias=False, accumulate_into=None
     smaller 1x1 -> X^T . dY as one hipBLASLt GEMM.  With f32 products the
     KxK go to MIOpen's igemm wrw, which beats the f32 MFMA kernel there."""
     KH, KW, Cin, Cout = w_shape
-    split = ops.conv.CONV_MATH == "split"
-    eligible = Cin % 4 == 0 and Cout % 4 == 0
     acc_w, acc_b = accumulate_into if accumulate_into is not None else (None, None)
 
-    def mfma(k, pads):
+    def added(gw):  # a path without the fused accumulate
+        return (gw if acc_w is None else acc_w.add_(gw)), None
+
+    route = _mfma_wgrad_route(x, gy, w_shape, stride, pb, pe)
+    if route is not None:
+        k, pads = route
         if want_bias and (acc_w is None or acc_b is not None):
             acc = (acc_w, acc_b) if acc_w is not None else None
             return ops.conv2d_wgrad(x, gy, k, stride, pads, with_bias=True, accumulate_into=acc,
                                     census=census)
         return ops.conv2d_wgrad(x, gy, k, stride, pads, accumulate_into=acc_w, census=census), None
+    if KH == 1 and KW == 1 and pb == 0 and pe == 0:
+        xs = x if stride == 1 else x[:, ::stride, ::stride]
+        xs = xs.reshape(-1, Cin)
+        return added(torch.mm(xs.t(), gy.reshape(-1, Cout)).reshape(1, 1, Cin, Cout))
+    xin = F.pad(x, (0, 0, pb, pe, pb, pe)) if (pb or pe) else x
+    gw = torch.nn.grad.conv2d_weight(xin.permute(0, 3, 1, 2), (Cout, Cin, KH, KW),
+                                     gy.permute(0, 3, 1, 2), stride, 0)
+    return added(gw.permute(2, 3, 1, 0))
 
-    def added(gw):  # a path without the fused accumulate
-        return (gw if acc_w is None else acc_w.add_(gw)), None
 
+def _mfma_wgrad_route(x, gy, w_shape, stride, pb, pe):
+    """(kernel size, pads) of the ops.conv2d_wgrad call _wgrad makes for this
+    shape, or None where it routes to hipBLASLt / MIOpen."""
+    KH, KW, Cin, Cout = w_shape
+    eligible = Cin % 4 == 0 and Cout % 4 == 0
     if KH == 1 and KW == 1 and pb == 0 and pe == 0:
         P = gy.numel() // Cout
         # tools/exp_wgrad_1x1.py: MFMA from 8400 pixels (res4: 54 vs 64-79 us
         # on hipBLASLt), and the strided 1024->2048 at 2100; hipBLASLt below
         if eligible and (P >= _WGRAD_1X1_MIN_P or (stride > 1 and Cin * Cout >= 2 ** 21)):
-            return mfma(1, (0, 0))
-        xs = x if stride == 1 else x[:, ::stride, ::stride]
-        xs = xs.reshape(-1, Cin)
-        return added(torch.mm(xs.t(), gy.reshape(-1, Cout)).reshape(1, 1, Cin, Cout))
-    if split and eligible and KH == KW and 6 * max(x.numel(), gy.numel()) < 2 ** 31:
-        return mfma(KH, (pb, pe))
-    xin = F.pad(x, (0, 0, pb, pe, pb, pe)) if (pb or pe) else x
-    gw = torch.nn.grad.conv2d_weight(xin.permute(0, 3, 1, 2), (Cout, Cin, KH, KW),
-                                     gy.permute(0, 3, 1, 2), stride, 0)
-    return added(gw.permute(2, 3, 1, 0))
+            return 1, (0, 0)
+        return None
+    if (ops.conv.CONV_MATH == "split" and eligible and KH == KW
+            and 6 * max(x.numel(), gy.numel()) < 2 ** 31):
+        return KH, (pb, pe)
+    return None
 
 
 # A side stream while the graphed training step captures its backward
@@ -183,6 +193,25 @@ def input_grad(links, gate_ok, dgrad):
     return plan.finish(dgrad(plan.gate, plan.add, plan.add2))
 
 
+def _defer_weight_grad(ctx, x, gy, w, stride, pb, pe, want_b, census):
+    """Leave this call's weight (and bias) gradient to the backward of the
+    batched fold whose output the weight is (handoff.WgradJoin): True when
+    deposited -- the MFMA route of _wgrad, no census, accumulator or side
+    stream, tuning "wgrad_group" on."""
+    entry = ctx.fold_entry
+    if (entry is None or not ctx.needs_input_grad[1] or census is not None
+            or _wgrad_stream is not None or not gy.is_cuda
+            or (ctx.links is not None and ctx.links.wacc is not None)
+            or ops.get_tuning("wgrad_group") <= 0):
+        return False
+    route = _mfma_wgrad_route(x, gy, w.shape, stride, pb, pe)
+    if route is None:
+        return False
+    join, index = entry
+    join.deposit((index, x, gy, route[0], stride, route[1], want_b))
+    return True
+
+
 def _weight_grad(ctx, x, gy, w, stride, pb, pe, want_b, census, side=None):
     """(weight, bias) gradient, None where not needed.  side: issued on that
     stream (wgrad_on) BEFORE the data gradient, so that the two run
@@ -240,6 +269,9 @@ class _ConvMFMAFn(torch.autograd.Function):
         ctx.save_for_backward(x, w_hwio, y if relu else None)
         ctx.conf = (stride, pads, relu, bias is not None, topdown is not None, residual is not None)
         ctx.links = links
+        # the weight is a batched fold's own output (no view, pad or cast in
+        # between): its gradient may wait for that fold's backward
+        ctx.fold_entry = handoff.tagged(w_hwio, handoff.FOLD_ENTRY)
         if links is not None:
             links.bind(x, topdown, residual is not None)
         ctx.out_tag = None
@@ -261,7 +293,10 @@ class _ConvMFMAFn(torch.autograd.Function):
         wg = (ctx, x, gy, w, stride, pb, pe, has_bias and ctx.needs_input_grad[2], census)
         side = _wgrad_stream
         forked = side is not None and ctx.needs_input_grad[1] and gy.is_cuda
-        if forked:
+        deferred = _defer_weight_grad(*wg)
+        if deferred:
+            gw = gb = None
+        elif forked:
             gw, gb = _weight_grad(*wg, side)
         gx = None
         if ctx.needs_input_grad[0]:
@@ -269,9 +304,9 @@ class _ConvMFMAFn(torch.autograd.Function):
                             lambda gate, add, add2: _dgrad(
                                 gy, w, x.shape, stride, pb, pe, relu_gate=x if gate else None,
                                 add=add, add2=add2, census=census))
-        if forked:
+        if forked and not deferred:
             _join_weight_grad(side, gw, gb)
-        else:
+        elif not deferred:
             gw, gb = _weight_grad(*wg)
         return gx, gw, gb, None, None, None, None, gtd, gres, None, None
 

@@ -78,6 +78,15 @@ grad_out, params) as set 0 and the second runs one backward over both sets.
 Unmerged: the first writes the full maps and leaves them, the second
 accumulates into them.
 
+``WgradJoin`` -- the weight gradients of the convs whose weight is a batched
+FrozenBN fold's output (the trainable backbone).  Nothing reads such a gradient
+before the fold's own backward, which runs once, after every conv's: each conv
+deposits its (input, output gradient, geometry) and returns no weight
+gradient, and the fold's backward computes all of them in one grouped launch
+per kernel family (ops.conv2d_wgrad_group): three launches and three reduces
+off the chain of data gradients instead of 36 + 36 inside it, with the bits of
+the single launches (tuning "wgrad_group" = 1; 2 also shortens the splits).
+
 Every protocol assumes that all its participants' backwards run in the same
 backward pass.  A backward that reaches only some of them (torch.autograd.grad
 or .backward on a subset of the losses, a loss that detaches one branch) would
@@ -138,6 +147,7 @@ STAGE_PAIR = "_d2mi_pair"        # a bottleneck input -> its conv1 / shortcut Pa
 TD_PAIR = "_d2mi_td_pair"        # an FPN merged map -> its output conv's Pair
 LEVEL_PAIR = "_d2mi_grad_pair"   # an FPN level -> its RPN conv / ROI pooler Pair
 ROW_BOUND = "_d2mi_row_bound"    # the RPN head's concatenated logits -> its RowBound
+FOLD_ENTRY = "_d2mi_fold_entry"  # a batched fold's w_eff -> (its WgradJoin, entry index)
 
 
 def tag(t, name, value):
@@ -491,6 +501,41 @@ class RowBound:
             raise HandoffError(f"row bound: level {level} was not published (or taken twice)")
         self._published[level] = RowBound._EMPTY
         return census
+
+
+class WgradJoin:
+    """The weight gradients of the convs that read one batched fold's outputs
+    (layers/ops/fold.py:_FoldManyFn), deferred to that fold's backward: nothing
+    reads a folded conv's weight gradient before it, and it runs once, after
+    every such conv's backward.  A conv whose weight IS the fold's output
+    (FOLD_ENTRY tag) deposits (entry, x, gy, stride, pads, want_bias) here and
+    returns no weight / bias gradient; the fold's backward takes every deposit
+    and computes them in one grouped launch per kernel family.  A backward
+    that ends with deposits left (the fold's backward did not run in it)
+    raises HandoffError and clears them."""
+    __slots__ = ("items", "label")
+
+    def __init__(self, label="deferred weight gradients"):
+        self.items = None
+        self.label = label
+
+    @property
+    def empty(self):
+        return self.items is None
+
+    def clear(self):
+        self.items = None
+
+    def deposit(self, item):
+        if self.items is None:
+            _deposit(self, "items", [item], self.label)
+        else:
+            self.items.append(item)
+            if OBSERVER is not None:
+                OBSERVER(self.label, "deposit")
+
+    def take_all(self):
+        return _take(self, "items", self.label) or []
 
 
 class PoolerShare:

@@ -20,7 +20,8 @@ from .boxes import (TOPK_MAX_K, apply_deltas, cascade_refine, grid_anchors,  # n
 from .conv import (CONV_FAMILIES, CONV_PLAN_FIELDS, LEVELS_PLAN_FIELDS, OP_ALIGNED,  # noqa: F401
                    OP_ALL_ALIGNED, OP_BIAS_ALIGNED, OP_GATE, OP_RESIDUAL, OP_TOPDOWN,
                    OP_WORKSPACE, OP_WS_ALIGNED, WGRAD_KERNELS, WGRAD_PLAN_FIELDS, RowCensus,
-                   column_sum, conv2d_nhwc, conv2d_nhwc_levels, conv2d_wgrad, conv_levels_plan,
+                   column_sum, conv2d_nhwc, conv2d_nhwc_levels, conv2d_wgrad, conv2d_wgrad_group,
+                   conv_levels_plan, wgrad_group_plan, WGRAD_FAMILIES,
                    conv_plan, pack_conv_weights, pack_conv_weights_many, preprocess_images,
                    row_census, row_census_workspace_size, skinny_levels_ok, split_bf16x3,
                    stem_conv, stem_conv_weights, stem_pool, stride_scatter, upsample2x_grad,

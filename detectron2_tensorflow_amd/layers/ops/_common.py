@@ -1,11 +1,14 @@
 """What every family module shares: tensor coercions, the box-regression and
 box-mode constants, and the tuning knobs with the workspace-size caches a
-knob change invalidates.  Imports no sibling module."""
+knob change invalidates, and the host tables that launches read from device
+memory (_HostTable).  Imports no sibling module."""
 import math
 
+import numpy as np
 import torch
 
 from ... import _C
+from ...utils import capture
 
 _DEFAULT_SCALE_CLAMP = math.log(1000.0 / 16)  # lib/modeling/box_regression.py:10
 
@@ -52,3 +55,30 @@ def set_tuning(key, value):
     _C.check(_C.lib().d2mi_set_tuning(key.encode(), int(value)), "d2mi_set_tuning")
     _CONV_WS.clear()
     _WGRAD_WS.clear()
+
+
+class _HostTable:
+    """A device copy of a host table uploaded through a small ring of pinned
+    buffers (each slot reused once its previous copy has left, by event)."""
+    RING = 4
+
+    def __init__(self, nbytes, device, what="table"):
+        self.what = what
+        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.ring = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
+        self.events = [None] * self.RING
+        self.i = 0
+
+    def upload(self, arr):
+        if capture.capturing():  # a per-graph table, filled after the capture
+            return capture.table(arr, self.dev.device, self.what)
+        k = self.i
+        self.i = (k + 1) % self.RING
+        if self.events[k] is not None:
+            self.events[k].synchronize()
+        self.ring[k].numpy()[:] = arr.view(np.uint8)
+        self.dev.copy_(self.ring[k], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.dev.device))
+        self.events[k] = ev
+        return self.dev

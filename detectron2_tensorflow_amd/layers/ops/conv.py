@@ -6,10 +6,11 @@ wgrad_skinny.hip), the stem (stem.hip) and the FPN / strided-conv adjoints
 ops.conv.CONV_MATH."""
 import os
 
+import numpy as np
 import torch
 
 from ... import _C
-from ._common import _CONV_WS, _WGRAD_WS, _f32c
+from ._common import _CONV_WS, _WGRAD_WS, _f32c, _HostTable
 from .timing import KernelTimer, bound_of, conv_bytes
 
 
@@ -368,6 +369,108 @@ def conv2d_wgrad(x, dy, kernel_size, stride=1, pad=(0, 0), with_bias=False, math
     return (dw, db) if with_bias else dw
 
 
+_WGRAD_PROBLEM_DT = np.dtype([(n, np.uint64) for n in ("x", "dy", "dw", "dbias")] + [
+    (n, np.int32) for n in ("N", "H", "W", "Cin", "Cout", "KH", "KW", "stride", "pad_beg",
+                            "pad_end")])
+WGRAD_GROUP_MAX = 64
+_wgrad_group_tables = {}
+
+
+def _wgrad_problems(shapes, ptrs=None):
+    """The host array of d2mi_conv2d_wgrad_group: shapes [(N, H, W, Cin, Cout, k,
+    stride, (pb, pe))], ptrs [(x, dy, dw, dbias)] device addresses (None: zeros)."""
+    tab = np.zeros(len(shapes), dtype=_WGRAD_PROBLEM_DT)
+    for i, (N, H, W, Cin, Cout, k, stride, (pb, pe)) in enumerate(shapes):
+        tab[i] = (ptrs[i] if ptrs else (0, 0, 0, 0)) + (N, H, W, Cin, Cout, k, k, stride, pb, pe)
+    return tab
+
+
+def conv2d_wgrad_group(problems, math_mode=None, out=None):
+    """conv2d_wgrad of many problems -- [(x, dy, kernel_size, stride, (pb, pe),
+    with_bias)] -> [(dw, db-or-None)] -- in one launch per kernel family and
+    one reduce per family (d2mi_conv2d_wgrad_group).  Tuning "wgrad_group" 1
+    (default): every problem keeps its own plan's pixel splits -- the bits of
+    conv2d_wgrad; 2: one chunks-per-split per family (few slabs, long walks,
+    sums in another order).  A group of one is conv2d_wgrad itself.  out: the dw tensors to
+    write (contiguous f32 HWIO, 4-byte aligned at least: gradient-bucket views)."""
+    math_mode = math_mode or CONV_MATH
+    if math_mode not in ("f32", "split"):
+        raise ValueError(f"conv math must be 'f32' or 'split', got {math_mode!r}")
+    if not problems:
+        return []
+    outs = []
+    for at in range(0, len(problems), WGRAD_GROUP_MAX):
+        outs += _wgrad_group(problems[at:at + WGRAD_GROUP_MAX], math_mode,
+                             None if out is None else list(out[at:at + WGRAD_GROUP_MAX]))
+    return outs
+
+
+def _wgrad_group(problems, math_mode, dws=None):
+    n = len(problems)
+    if n == 1 and dws is None:
+        x, dy, k, stride, pad, with_bias = problems[0]
+        r = conv2d_wgrad(x, dy, k, stride, pad, with_bias=with_bias, math_mode=math_mode)
+        return [r if with_bias else (r, None)]
+    xs = [_f32c(p[0]) for p in problems]
+    dys = [_f32c(p[1]) for p in problems]
+    _C.require_device(*xs, *dys)
+    dev = xs[0].device
+    shapes = []
+    for x, dy, p in zip(xs, dys, problems):
+        N, H, W, Cin = x.shape
+        shapes.append((N, H, W, Cin, dy.shape[-1], int(p[2]), int(p[3]),
+                       (int(p[4][0]), int(p[4][1]))))
+    sizes = [s[5] * s[5] * s[3] * s[4] for s in shapes]
+    couts = [s[4] if p[5] else 0 for s, p in zip(shapes, problems)]
+    if dws is None:  # one allocation for the gradients (every size is a multiple of 4 floats)
+        flat = torch.empty(sum(sizes) + sum(couts), dtype=torch.float32, device=dev)
+        parts = flat.split(sizes + couts)
+        dws = [parts[i].view(s[5], s[5], s[3], s[4]) for i, s in enumerate(shapes)]
+        dbs = [parts[n + i] if couts[i] else None for i in range(n)]
+    else:
+        for dw, s in zip(dws, shapes):
+            if (tuple(dw.shape) != (s[5], s[5], s[3], s[4]) or dw.dtype != torch.float32
+                    or not dw.is_contiguous() or dw.device != dev):
+                raise ValueError("conv2d_wgrad_group: out must be contiguous f32 HWIO tensors")
+        dbs = [torch.empty((c,), dtype=torch.float32, device=dev) if c else None for c in couts]
+    flags = 4 if math_mode == "split" else 0
+    tab = _wgrad_problems(shapes, [(x.data_ptr(), dy.data_ptr(), dw.data_ptr(),
+                                    0 if db is None else db.data_ptr())
+                                   for x, dy, dw, db in zip(xs, dys, dws, dbs)])
+    lib = _C.lib()
+    # (asked every call: the group's plan moves with the wgrad_* tuning knobs)
+    # (a group without slabs still needs a workspace to be planned as a group)
+    wsb = max(lib.d2mi_conv2d_wgrad_group_workspace_size(tab.ctypes.data, n, flags), 256)
+    ws = _C.scratch(wsb, dev)
+    tkey = (n, dev)
+    table = _wgrad_group_tables.get(tkey)
+    if table is None:
+        table = _wgrad_group_tables[tkey] = _HostTable(
+            lib.d2mi_conv2d_wgrad_group_table_size(n), dev, "wgrad group")
+    host = np.empty(table.dev.numel(), dtype=np.uint8)
+    rc = lib.d2mi_conv2d_wgrad_group_table(tab.ctypes.data, n, flags, _C.ptr(ws), wsb,
+                                           host.ctypes.data, host.size)
+    _C.check(rc, "d2mi_conv2d_wgrad_group_table")
+    dev_tab = table.upload(host)
+    ev = KernelTimer.start()
+    rc = lib.d2mi_conv2d_wgrad_group(tab.ctypes.data, n, flags, _C.ptr(dev_tab), host.size,
+                                     _C.ptr(ws), wsb, _C.stream_of(dev))
+    fl = sum(2.0 * dy.numel() * s[5] * s[5] * s[3] for dy, s in zip(dys, shapes))
+    group = "conv2d_wgrad_split" if flags & 4 else "conv2d_wgrad_mfma"
+    KernelTimer.stop(ev, group, fl)
+    if ev is not None:
+        byts = 4.0 * (sum(x.numel() + dy.numel() for x, dy in zip(xs, dys)) + sum(sizes)
+                      + sum(couts))
+        KernelTimer.stop(ev, f"{group}_{bound_of(fl, byts, math_mode)}_bound", fl,
+                         extra=lambda: {"bytes": byts})
+        if KernelTimer.detail:
+            KernelTimer.stop(ev, f"wgrad_group[{n}] " + " ".join(sorted(
+                {f"{s[3]}->{s[4]}k{s[5]}s{s[6]}" for s in shapes})), fl,
+                extra=lambda: {"bytes": byts})
+    _C.check(rc, "d2mi_conv2d_wgrad_group")
+    return list(zip(dws, dbs))
+
+
 # ------------------------------------------------------------- plan queries
 # The launch plans of the three conv families as dicts (d2mi_conv2d_plan and
 # its kin, include/d2mi.h: the planner the launchers run; no GPU needed).
@@ -435,6 +538,43 @@ def wgrad_plan(N, H, W, Cin, Cout, k, stride=1, pad=(0, 0), flags=4,
     v, wsb = _plan_query(lib.d2mi_conv2d_wgrad_plan, "d2mi_conv2d_wgrad_plan", args, flags,
                          operands, workspace_bytes, len(WGRAD_PLAN_FIELDS) + 2)
     return dict(zip(WGRAD_PLAN_FIELDS, v), workspace_bytes=wsb)
+
+
+WGRAD_FAMILIES = ("ws", "ws_inc", "split2x2", "split2x1", "split1x2", "split1x1", "split2x2_occ3")
+WGRAD_GROUP_FAMILY_FIELDS = ("problems", "workgroups", "chunks_per_split", "reduce_problems",
+                             "reduce_grid")
+WGRAD_GROUP_PROBLEM_FIELDS = ("family", "kernel", "tiles", "nchunks", "splits", "chunks_per_split",
+                              "wg0")
+
+
+def wgrad_group_plan(shapes, flags=4, operands=OP_WORKSPACE | OP_WS_ALIGNED, workspace_bytes=None):
+    """The plan of conv2d_wgrad_group (no GPU needed); shapes: [(N, H, W, Cin,
+    Cout, k, stride, (pb, pe))].  {"grouped", "families": {name: {...}},
+    "problems": [{..., "slab_offset" (bytes), "slab_bytes"}], "workspace_bytes"}."""
+    tab = _wgrad_problems(shapes)
+    n = len(shapes)
+    lib = _C.lib()
+    if workspace_bytes is None:
+        workspace_bytes = lib.d2mi_conv2d_wgrad_group_workspace_size(tab.ctypes.data, n, flags)
+    nf, npf = len(WGRAD_FAMILIES), len(WGRAD_GROUP_PROBLEM_FIELDS)
+    m = 2 + 6 * nf + (npf + 2) * n + 2
+    out = (_C.ctypes.c_int32 * m)()
+    rc = lib.d2mi_conv2d_wgrad_group_plan(tab.ctypes.data, n, int(flags), int(operands),
+                                          int(workspace_bytes), out, m)
+    _C.check(min(rc, 0), "d2mi_conv2d_wgrad_group_plan")
+    v = list(out)
+    fams = {name: dict(zip(WGRAD_GROUP_FAMILY_FIELDS, v[2 + 6 * f:8 + 6 * f]))
+            for f, name in enumerate(WGRAD_FAMILIES)}
+    probs = []
+    for i, s in enumerate(shapes):
+        pv = v[2 + 6 * nf + (npf + 2) * i:][:npf + 2]
+        d = dict(zip(WGRAD_GROUP_PROBLEM_FIELDS, pv))
+        d["slab_offset"] = pv[npf] | (pv[npf + 1] << 31)
+        d["slab_bytes"] = (d["splits"] * (s[5] * s[5] * s[3] * s[4] + s[4]) * 4
+                           if v[0] and d["splits"] > 1 else 0)
+        probs.append(d)
+    return {"grouped": v[0], "families": fams, "problems": probs,
+            "workspace_bytes": v[-2] | (v[-1] << 31)}
 
 
 def stem_conv_weights(w):

@@ -6,7 +6,9 @@ import torch
 
 from ... import _C
 from ...utils import capture
-from ._common import _f32c
+from .. import handoff
+from ._common import _f32c, _HostTable
+from .conv import conv2d_wgrad_group
 
 
 class _FoldFrozenBNFn(torch.autograd.Function):
@@ -76,33 +78,6 @@ _FOLD_DT = np.dtype([(n, np.uint64) for n in (
     ("partial_offset", np.int64)])
 
 
-class _HostTable:
-    """A device copy of a host table uploaded through a small ring of pinned
-    buffers (each slot reused once its previous copy has left, by event)."""
-    RING = 4
-
-    def __init__(self, nbytes, device, what="table"):
-        self.what = what
-        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        self.ring = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
-        self.events = [None] * self.RING
-        self.i = 0
-
-    def upload(self, arr):
-        if capture.capturing():  # a per-graph table, filled after the capture
-            return capture.table(arr, self.dev.device, self.what)
-        k = self.i
-        self.i = (k + 1) % self.RING
-        if self.events[k] is not None:
-            self.events[k].synchronize()
-        self.ring[k].numpy()[:] = arr.view(np.uint8)
-        self.dev.copy_(self.ring[k], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.dev.device))
-        self.events[k] = ev
-        return self.dev
-
-
 _fold_tables = {}
 
 
@@ -164,17 +139,25 @@ class _FoldManyFn(torch.autograd.Function):
     (one launch) forward, d2mi_fold_frozen_bn_bwd_many (two launches)
     backward.  inputs: per entry (w, bias, gamma, beta, mean, var); outputs:
     per entry (w_eff, b_eff, packed-or-None).  Repeated folds of the same
-    parameters run from a _FoldPlan."""
+    parameters run from a _FoldPlan.
+
+    Every w_eff carries (a handoff.WgradJoin, its entry index) as its
+    FOLD_ENTRY tag: a conv whose weight is that very tensor may leave its
+    weight gradient to this node's backward (layers/conv_grad.py), which
+    computes every deposited one in one grouped launch per kernel family
+    (ops.conv2d_wgrad_group) before the fold adjoint."""
 
     @staticmethod
     def forward(ctx, spec, *ts):
         n = len(spec)
         dev = ts[0].device
+        ctx.join = handoff.WgradJoin()
         key = (spec, dev, tuple(_addr(t) for t in ts), tuple(ts[6 * i].shape for i in range(n)))
         plan = None if capture.capturing() else _fold_plans.get(key)
         if plan is not None and plan.reusable():
             outs = plan.views()
             for i in range(n):
+                handoff.tag(outs[3 * i], handoff.FOLD_ENTRY, (ctx.join, i))
                 if outs[3 * i + 2] is not None:
                     ctx.mark_non_differentiable(outs[3 * i + 2])
             rc = _C.lib().d2mi_fold_frozen_bn_many(_C.ptr(plan.dev_tab), n, plan.fwd,
@@ -217,6 +200,7 @@ class _FoldManyFn(torch.autograd.Function):
             cob += Cout
             part += chunks * Cout
             outs += [w_eff, b_eff, packed]
+            handoff.tag(w_eff, handoff.FOLD_ENTRY, (ctx.join, i))
             if packed is not None:
                 ctx.mark_non_differentiable(packed)
         tab = np.array(rows, dtype=_FOLD_DT)
@@ -246,9 +230,20 @@ class _FoldManyFn(torch.autograd.Function):
         ret = [None]
         keep = []
         cols = [[0] * n for _ in range(6)]  # gw_eff gb_eff gw gbias ggamma gbeta
+        # the weight gradients the convs left to this backward: one grouped call
+        late = {}
+        items = ctx.join.take_all()
+        if items:
+            for (i, *_), g in zip(items, conv2d_wgrad_group([it[1:] for it in items])):
+                late.setdefault(i, []).append(g)
+        del items
         for i in range(n):
             w, bias, gamma, beta = ts[6 * i:6 * i + 4]
             gw_eff, gb_eff = grads[3 * i], grads[3 * i + 1]
+            for dw, db in late.get(i, ()):
+                gw_eff = dw if gw_eff is None else gw_eff + dw
+                if db is not None:
+                    gb_eff = db if gb_eff is None else gb_eff + db
             if gw_eff is not None:
                 gw_eff = _f32c(gw_eff)
             if gb_eff is not None:

@@ -96,7 +96,14 @@ const char* d2mi_last_error(void);
  *   "wgrad_prio"   wave priority 1 while issuing MFMAs in the weight gradient
  *                  (1 on);
  *   "topk_floor"   sampled-floor first pass of the segmented top-k (1); 0 =
- *                  radix passes only. */
+ *                  radix passes only;
+ *   "wgrad_group"  the folded convs' weight gradients deferred to the fold's
+ *                  backward and launched per kernel family
+ *                  (d2mi_conv2d_wgrad_group): 1 (default) = every problem keeps
+ *                  the pixel splits of its own plan, bit-identical to its
+ *                  single launch; 2 = one chunks-per-split per family (few
+ *                  slabs, long walks; sums in another order); 0 = each in its
+ *                  own backward. */
 int d2mi_set_tuning(const char* key, int value);
 /* Current value of a d2mi_set_tuning key (INT32_MIN for an unknown key). */
 int d2mi_get_tuning(const char* key);
@@ -824,6 +831,45 @@ int d2mi_conv2d_wgrad_ex(const float* x, const float* dy, float* dw_hwio, float*
                          int H, int W, int Cin, int Cout, int KH, int KW, int stride,
                          int pad_beg, int pad_end, int flags, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* Many weight gradients in one launch per kernel family (flags bit2 as
+ * d2mi_conv2d_wgrad_ex; no accumulate).  problems: a HOST array of n (<= 64)
+ *   struct { const float* x; const float* dy; float* dw; float* dbias;
+ *            int32_t N, H, W, Cin, Cout, KH, KW, stride, pad_beg, pad_end; }
+ * (72 bytes each; dbias nullable).  Alone, a small weight gradient cuts its
+ * pixels into many splits to fill the chip; in a group the problems of one
+ * kernel family share one grid and one reduce launch.  Under tuning
+ * "wgrad_group" = 1 each keeps the splits of its own d2mi_conv2d_wgrad_plan
+ * (the same sums in the same order: the bits of d2mi_conv2d_wgrad_ex); under 2
+ * a family has one common chunks-per-split, chosen from its summed tile-chunks
+ * against rounds of resident workgroups: long pixel walks, few partial slabs.
+ * A problem of one split writes dw directly.  A group of one runs exactly
+ * d2mi_conv2d_wgrad_ex; so does every problem when the workspace is missing,
+ * short or not 16-byte aligned, and every problem on the f32 kernels.
+ *
+ * The launches read their arguments from a device table.  The caller gets its
+ * bytes from d2mi_conv2d_wgrad_group_table (host only: it writes table_bytes =
+ * d2mi_conv2d_wgrad_group_table_size(n) bytes for THIS workspace address into
+ * table_host), copies them to the device in stream order (or, for a captured
+ * launch, any time before the replay) and passes that copy as table_dev.
+ *
+ * d2mi_conv2d_wgrad_group_plan: 2 + 7 * 6 + n * 9 + 2 integers --
+ *   [0] grouped (0: the per-problem plans)  [1] n;
+ *   per family f = 0..6 (ws, ws_inc, split 2x2, 2x1, 1x2, 1x1, 2x2 at three
+ *   per CU): problems, workgroups, chunks per split, problems with slabs,
+ *   reduce grid, 0;
+ *   per problem (9): family (-1: alone), kernel, tiles, chunks, splits, chunks
+ *   per split, first workgroup, slab byte offset as lo + hi * 2^31;
+ *   then lo + hi * 2^31 = workspace bytes. */
+size_t d2mi_conv2d_wgrad_group_workspace_size(const void* problems, int n, int flags);
+size_t d2mi_conv2d_wgrad_group_table_size(int n);
+int d2mi_conv2d_wgrad_group_plan(const void* problems, int n, int flags, int operands,
+                                 size_t workspace_bytes, int32_t* out, int out_len);
+int d2mi_conv2d_wgrad_group_table(const void* problems, int n, int flags, void* workspace,
+                                  size_t workspace_bytes, void* table_host, size_t table_bytes);
+int d2mi_conv2d_wgrad_group(const void* problems, int n, int flags, const void* table_dev,
+                            size_t table_bytes, void* workspace, size_t workspace_bytes,
+                            void* stream);
 
 /* Row census of a sparse gradient map g [N*H*W][C] (C % 4 == 0), for a
  * gradient whose producer can bound its non-zero rows (the RPN loss: at most

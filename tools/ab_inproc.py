@@ -87,7 +87,12 @@ def _skinny_levels(on):
     _RPNHead1x1Fn.LEVELS_ONE_LAUNCH = on
 
 
-SWITCHES = {"skinny_levels": _skinny_levels, "mask_prep_early": _mask_prep_early, "gc_off": _gc_off, "defer_pixels": _defer_pixels, "rpn_concat": _rpn_concat, "rpn_conv_acc": _rpn_conv_acc, "fpn_join": _fpn_join, "pack_group": _pack_group, "rpn_acc": _rpn_acc,
+def _wgrad_group(on):
+    from detectron2_tensorflow_amd.layers import ops
+    ops.set_tuning("wgrad_group", 1 if on else 0)
+
+
+SWITCHES = {"wgrad_group": _wgrad_group, "skinny_levels": _skinny_levels, "mask_prep_early": _mask_prep_early, "gc_off": _gc_off, "defer_pixels": _defer_pixels, "rpn_concat": _rpn_concat, "rpn_conv_acc": _rpn_conv_acc, "fpn_join": _fpn_join, "pack_group": _pack_group, "rpn_acc": _rpn_acc,
             "conv_epi": _conv_epi,
             "wgrad_ws1": _wgrad_ws1, "stem_mfma": _stem_mfma, "fused_sample": _fused_sample}
 
